@@ -18,6 +18,14 @@ Each torchrun rank hosts one single-GPU faabric_amd worker process; rank 0
 also runs the planner and submits the gang-scheduled MPI batch. Rank
 functions are native C++ (cpp/src/bench_funcs.cpp) — Python never touches
 the timed path.
+
+A plain run sets up, warms up, times the steps and prints the result line.
+`--full` adds the measurements that take runs of their own (the config-4
+GPU snapshot diff+merge sub-benchmark; its `snapshot_*` fields are 0
+without it). `--dump-outputs DIR` writes what the last timed step computed
+as `DIR/<name>.npy` (float32): the allreduce and alltoall receive buffers
+and the return value of every kvtouch function. Inputs are fixed fill
+patterns, so two runs with the same arguments dump identical arrays.
 """
 
 import argparse
@@ -57,7 +65,40 @@ def parse_args():
     p.add_argument("--snap-bytes", type=int, default=4 * 1024 * 1024 * 1024,
                    help="per-rank GPU snapshot diff+merge region (config 4: "
                         "4 GB random-byte region per GPU)")
+    p.add_argument("--full", action="store_true",
+                   help="also run the measurements beyond the headline "
+                        "figure (GPU snapshot diff+merge sub-benchmark)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the last timed step's outputs as DIR/*.npy")
     return p.parse_args()
+
+
+# Budget for --dump-outputs: three arrays of at most 16 MB each
+DUMP_MAX_ELEMS = 4 * 1024 * 1024
+
+
+def dump_outputs(out_dir, raw):
+    """Write the rank-0 outputs of the last timed step as float32 .npy
+    files. An array above DUMP_MAX_ELEMS is cut to a fixed, seeded sample
+    of its elements (same indices for the same array length)."""
+    import numpy as np
+
+    arrays = {
+        "allreduce": np.frombuffer(raw["allreduce"], dtype=np.float32),
+    }
+    if "alltoall" in raw:
+        arrays["alltoall"] = np.frombuffer(raw["alltoall"], dtype=np.uint8)
+    if "batch_return_values" in raw:
+        arrays["batch_return_values"] = np.frombuffer(
+            raw["batch_return_values"], dtype=np.int32)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in arrays.items():
+        if arr.size > DUMP_MAX_ELEMS:
+            rng = np.random.default_rng(0)
+            idx = np.sort(rng.integers(0, arr.size, size=DUMP_MAX_ELEMS))
+            arr = arr[idx]
+        np.save(os.path.join(out_dir, name + ".npy"),
+                arr.astype(np.float32))
 
 
 def main():
@@ -125,11 +166,14 @@ def main():
         # Gang placement: rank i on worker i (preloaded decision)
         # ping-pong reuses the allreduce buffers: clamp to their size
         pp = min(args.pp_bytes, args.bytes) if n >= 2 else 0
+        # The snapshot sub-benchmark is a measurement of its own: --full only
+        snap_bytes = args.snap_bytes if have_gpu and args.full else 0
         params = (
             f"steps={args.steps};warmup={args.warmup};bytes={args.bytes};"
             f"batch={args.batch};kvbytes={args.kv_bytes};"
             f"a2abytes={args.a2a_bytes};ppbytes={pp};"
-            f"snapbytes={args.snap_bytes if have_gpu else 0}"
+            f"snapbytes={snap_bytes};"
+            f"dump={1 if args.dump_outputs else 0}"
         )
         ber = _core.batch_exec_factory("bench", "rankstep", 1)
         msgs = ber.messages
@@ -188,6 +232,7 @@ def main():
         snap_apply_total = sum(v[0] for v in snap_apply if v)
         snap_region_total = sum(v[0] for v in snap_region if v)
         k = min(len(s) for s in per_rank_step)
+        assert k == args.steps, f"timed {k} steps, asked for {args.steps}"
         step_ms = [max(s[i] for s in per_rank_step) for i in range(k)]
         ar_ms = [max(s[i] for s in per_rank_ar) for i in range(k)]
         batch_ms = [max(s[i] for s in per_rank_batch) for i in range(k)]
@@ -246,7 +291,8 @@ def main():
                 "batch_msgs_per_sec": round(msgs_per_sec, 2),
                 "batch_ms": round(batch_mean_ms, 3),
                 "kv_bytes": args.kv_bytes,
-                "snapshot_bytes_per_rank": args.snap_bytes if have_gpu else 0,
+                "full": args.full,
+                "snapshot_bytes_per_rank": snap_bytes,
                 "snapshot_diff_gbps_total": round(snap_diff_total, 2),
                 "snapshot_apply_gbps_total": round(snap_apply_total, 2),
                 "snapshot_diff_region_gbps_total":
@@ -261,6 +307,8 @@ def main():
     if dist is not None:
         dist.barrier()
     if RANK == 0 and result is not None:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, _core.bench_last_outputs())
         print(json.dumps(result), flush=True)
         if os.environ.get("FAABRIC_PROF"):
             print(_core.prof_summary(), file=sys.stderr, flush=True)

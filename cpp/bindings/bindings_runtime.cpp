@@ -23,6 +23,7 @@ using namespace faabricamd;
 
 namespace faabricamd {
 void registerBenchFunctions();       // bench_funcs.cpp
+std::map<std::string, std::vector<uint8_t>> benchLastOutputs();
 void registerMpiExampleFunctions();  // mpi_examples.cpp
 }
 
@@ -915,6 +916,15 @@ void initRuntimeBindings(py::module_& m)
         return Scheduler::get().reapStaleExecutors();
     });
     m.def("register_bench_functions", [] { registerBenchFunctions(); });
+    // Outputs of the last bench/rankstep run with dump=1 (name -> bytes)
+    m.def("bench_last_outputs", [] {
+        py::dict d;
+        for (const auto& [name, data] : benchLastOutputs()) {
+            d[py::str(name)] =
+              py::bytes((const char*)data.data(), data.size());
+        }
+        return d;
+    });
     m.def("register_mpi_example_functions",
           [] { registerMpiExampleFunctions(); });
 

@@ -21,6 +21,8 @@
 
 #include <cmath>
 #include <cstring>
+#include <map>
+#include <mutex>
 #include <sstream>
 
 namespace faabricamd {
@@ -39,6 +41,17 @@ static std::map<std::string, int64_t> parseParams(const Message& msg)
         }
     }
     return out;
+}
+
+// What the last rankstep run in this process computed in its final step,
+// kept only when the caller asked for it (dump=1): name -> raw bytes
+static std::mutex lastOutputsMx;
+static std::map<std::string, std::vector<uint8_t>> lastOutputs;
+
+std::map<std::string, std::vector<uint8_t>> benchLastOutputs()
+{
+    std::lock_guard<std::mutex> lock(lastOutputsMx);
+    return lastOutputs;
 }
 
 static int32_t benchKvTouch(Message& msg)
@@ -90,6 +103,8 @@ static int32_t benchRankStep(Message& msg)
     int64_t ppBytes = params.count("ppbytes") ? params["ppbytes"] : 0;
     int64_t snapBytes =
       params.count("snapbytes") ? params["snapbytes"] : 0;
+    bool dump = params.count("dump") && params["dump"] != 0;
+    int32_t lastBatchAppId = 0;
 
     int nGpus = 0;
     (void)hipGetDeviceCount(&nGpus);
@@ -283,6 +298,7 @@ static int32_t benchRankStep(Message& msg)
             // the last result lands (no status polls contending with
             // result ingestion on the planner lock)
             getPlannerClient().waitBatchDone(ber->appId, 120000);
+            lastBatchAppId = ber->appId;
         }
         world.barrier(rank); // every host's batch functions returned
         // Group-commit: drain this host's pending HBM KV writes inside
@@ -299,6 +315,45 @@ static int32_t benchRankStep(Message& msg)
             pingpongMs.push_back((tPp1 - tPp0) / 1000.0);
             ringMs.push_back((tRing1 - tRing0) / 1000.0);
         }
+    }
+
+    // Keep what the last step left in the receive buffers (and what its
+    // batch returned) for the caller to write out; outside the timed steps
+    if (dump) {
+        std::map<std::string, std::vector<uint8_t>> outs;
+        auto grab = [&](const char* name, const uint8_t* src, size_t n) {
+            std::vector<uint8_t>& dst = outs[name];
+            dst.resize(n);
+            if (!onGpu) {
+                std::memcpy(dst.data(), src, n);
+                return true;
+            }
+            return hipMemcpy(dst.data(), src, n, hipMemcpyDeviceToHost) ==
+                   hipSuccess;
+        };
+        bool ok = grab("allreduce", recvBuf, count * sizeof(float));
+        if (ok && a2aBytes > 0) {
+            ok = grab("alltoall", a2aRecv, (size_t)a2aBytes * worldSize);
+        }
+        if (!ok) {
+            msg.outputData = "copying outputs to the host failed";
+            return 1;
+        }
+        if (lastBatchAppId != 0) {
+            // Return value of every kvtouch function, in app-index order
+            auto status = getPlannerClient().getBatchResults(lastBatchAppId);
+            std::vector<int32_t> rvs(status.messageResults.size(), -1);
+            for (const auto& m : status.messageResults) {
+                if (m.appIdx >= 0 && (size_t)m.appIdx < rvs.size()) {
+                    rvs[m.appIdx] = m.returnValue;
+                }
+            }
+            std::vector<uint8_t>& dst = outs["batch_return_values"];
+            dst.resize(rvs.size() * sizeof(int32_t));
+            std::memcpy(dst.data(), rvs.data(), dst.size());
+        }
+        std::lock_guard<std::mutex> lock(lastOutputsMx);
+        lastOutputs.swap(outs);
     }
 
     if (onGpu) {

@@ -45,6 +45,50 @@ def test_bench_single_rank():
     assert parsed["config"]["global_batch"] == 8
 
 
+def test_bench_dump_outputs_repeatable(tmp_path):
+    """--dump-outputs writes the last timed step's outputs as float32
+    .npy files, identical from run to run; --full is accepted and keeps
+    the result line's schema."""
+    import numpy as np
+
+    env = {**os.environ, "FAABRIC_BENCH_BASE_OFFSET": "12300",
+           "LOG_LEVEL": "error"}
+    base = [sys.executable, "bench.py", "--gpus", "1", "--steps", "3",
+            "--warmup", "1", "--batch", "8", "--bytes", str(1 << 20)]
+    first = run_bench(base + ["--dump-outputs", str(tmp_path / "a")], env)
+    second = run_bench(
+        base + ["--full", "--dump-outputs", str(tmp_path / "b")], env)
+    for parsed in (first, second):
+        for f in REQUIRED_FIELDS:
+            assert f in parsed, f
+        assert parsed["steps"] == 3
+        assert parsed["ms_per_step"] > 0
+    assert first["config"]["full"] is False
+    assert second["config"]["full"] is True
+
+    names = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert names == ["allreduce.npy", "alltoall.npy",
+                     "batch_return_values.npy"]
+    total = 0
+    for name in names:
+        a = np.load(tmp_path / "a" / name)
+        b = np.load(tmp_path / "b" / name)
+        assert a.dtype == np.float32
+        assert a.size > 0
+        assert np.array_equal(a, b), name
+        total += a.nbytes
+    assert total <= 64 * 1024 * 1024
+    # 1-rank world: both collectives hand back the fill pattern sent
+    fill = np.frombuffer(b"\x3f" * 4, dtype=np.float32)[0]
+    ar = np.load(tmp_path / "a" / "allreduce.npy")
+    assert ar.size == (1 << 20) // 4
+    assert np.all(ar == fill)
+    assert np.all(np.load(tmp_path / "a" / "alltoall.npy") == 0x11)
+    rvs = np.load(tmp_path / "a" / "batch_return_values.npy")
+    assert rvs.size == 8
+    assert np.all(rvs == 0)
+
+
 def test_bench_torchrun_two_ranks():
     """The N>1 launch shape the driver uses (one rank per GPU; gloo/host
     plane on CPU here)."""

@@ -83,12 +83,27 @@ def test_not_enough_slots(runtime):
 
 
 def test_sequential_batches_reuse_executors(runtime):
-    results = execute_batch("demo", "noop", 4)
+    # A no-op can finish (and release its executor) before the next
+    # message of the same batch is dispatched, so how many executors a
+    # no-op batch needs depends on thread timing. The barrier holds all 4
+    # functions of a batch in flight together: every batch needs exactly 4
+    barrier = threading.Barrier(4)
+
+    def rendezvous(msg):
+        barrier.wait(timeout=20)
+        return 0
+
+    _core.register_function("demo", "rendezvous", rendezvous)
+    count_before = _core.get_executor_count()
+    results = execute_batch("demo", "rendezvous", 4)
     assert len(results) == 4
+    assert all(r.return_value == 0 for r in results)
     count_after_first = _core.get_executor_count()
+    assert count_after_first == count_before + 4
     for _ in range(3):
-        results = execute_batch("demo", "noop", 4)
+        results = execute_batch("demo", "rendezvous", 4)
         assert len(results) == 4
+        assert all(r.return_value == 0 for r in results)
     # Warm executors are reused, not recreated per batch
     assert _core.get_executor_count() == count_after_first
 

@@ -105,6 +105,51 @@ def test_bench_functions_on_gpu(runtime):
     assert "step:" in results[0].output_data
 
 
+@requires_gpu
+def test_bench_rankstep_keeps_last_outputs(runtime):
+    """dump=1 keeps the last step's device receive buffers and batch
+    return values for the caller (bench.py --dump-outputs)."""
+    _core.register_bench_functions()
+    # the rank itself holds one of the runtime's 8 slots: batch of 4 fits
+    params = (b"steps=2;warmup=1;bytes=4194304;batch=4;kvbytes=4096;"
+              b"a2abytes=65536;dump=1")
+    results = submit_mpi("bench", "rankstep", 1, input_data=params)
+    assert results[0].return_value == 0, results[0].output_data
+    outs = _core.bench_last_outputs()
+    assert outs["allreduce"] == b"\x3f" * 4194304
+    assert outs["alltoall"] == b"\x11" * 65536
+    assert struct.unpack("<4i", outs["batch_return_values"]) == (0,) * 4
+
+
+@requires_gpu
+def test_bench_full_runs_snapshot_subbench():
+    """bench.py --full adds the GPU snapshot diff+merge sub-benchmark to
+    the plain run's result line."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    repo_root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run(
+        [sys.executable, "bench.py", "--gpus", "1", "--steps", "2",
+         "--warmup", "1", "--batch", "8", "--bytes", str(4 << 20),
+         "--snap-bytes", str(64 << 20), "--full"],
+        cwd=repo_root,
+        env={**os.environ, "FAABRIC_BENCH_BASE_OFFSET": "14000",
+             "LOG_LEVEL": "error"},
+        capture_output=True, text=True, timeout=240,
+    )
+    assert out.returncode == 0, out.stderr[-3000:]
+    parsed = json.loads(
+        [l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+    assert parsed["steps"] == 2
+    assert parsed["config"]["full"] is True
+    assert parsed["config"]["snapshot_bytes_per_rank"] == 64 << 20
+    assert parsed["config"]["snapshot_diff_gbps_total"] > 0
+    assert parsed["config"]["snapshot_apply_gbps_total"] > 0
+
+
 # ---------------------------------------------------------------------------
 # gfx950 snapshot-engine kernels: numerics vs a plain torch reference
 # ---------------------------------------------------------------------------
