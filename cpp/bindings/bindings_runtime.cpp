@@ -902,6 +902,42 @@ void initRuntimeBindings(py::module_& m)
         d["decision_cache"] = DecisionCache::get().size();
         return d;
     });
+    // Device-KV commit counters: famCommitPages launches / pages listed
+    m.def("_debug_kv_commit_stats", [] {
+        KvCommitStats s = kvCommitStats();
+        py::dict d;
+        d["launches"] = s.launches;
+        d["pages"] = s.pages;
+        return d;
+    });
+    // The device-KV dirty-bitmap sweep on a bitmap of n_pages pages with
+    // the given bits set: returns (swept page list, bitmap words after)
+    m.def("_debug_kv_sweep_bitmap",
+          [](size_t nPages, const std::vector<uint64_t>& setBits) {
+              size_t nWords = (nPages + 63) / 64;
+              auto words = std::make_unique<std::atomic<uint64_t>[]>(
+                std::max<size_t>(nWords, 1));
+              for (size_t w = 0; w < nWords; w++) {
+                  words[w].store(0);
+              }
+              for (uint64_t b : setBits) {
+                  if (b >= nPages) {
+                      throw FaabricException("bit beyond the bitmap");
+                  }
+                  words[b / 64].fetch_or(1ULL << (b % 64));
+              }
+              std::vector<uint32_t> pages(nPages);
+              size_t n =
+                kvSweepDirtyBitmap(words.get(), nPages, pages.data());
+              pages.resize(n);
+              std::vector<uint64_t> after(nWords);
+              for (size_t w = 0; w < nWords; w++) {
+                  after[w] = words[w].load();
+              }
+              return py::make_tuple(pages, after);
+          },
+          py::arg("n_pages"),
+          py::arg("set_bits"));
     m.def("wait_batch_done",
           [](int32_t appId, int timeoutMs) {
               py::gil_scoped_release release;

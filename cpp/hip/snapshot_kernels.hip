@@ -419,6 +419,43 @@ __global__ __launch_bounds__(FAM_KERNEL_BLOCK) void touchPagesKernel(
     }
 }
 
+// ---------------------------------------------------------------------------
+// State-KV mirror commit: scatter the listed 4 KiB pages of a pinned host
+// mirror to the same offsets of the HBM value. One block per listed page,
+// one 16 B load (over the host link) + one 16 B store per lane. `src` and
+// `pageIdx` are device-visible pointers to pinned host memory, read in
+// place. The value's last page may be partial and its tail need not be a
+// multiple of 16 B: exactly min(4096, valueBytes - page*4096) bytes are
+// copied, nothing past the value is read or written.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(FAM_KERNEL_BLOCK) void famKvCommitPagesKernel(
+  const u8* __restrict__ src,
+  u8* __restrict__ dst,
+  const u32* __restrict__ pageIdx,
+  u32 nPages,
+  u64 valueBytes)
+{
+    u32 slot = blockIdx.x;
+    if (slot >= nPages) {
+        return;
+    }
+    u64 base = (u64)pageIdx[slot] * FAM_PAGE;
+    if (base >= valueBytes) {
+        return;
+    }
+    u64 left = valueBytes - base;
+    u32 n = left < FAM_PAGE ? (u32)left : (u32)FAM_PAGE;
+    u32 off = threadIdx.x * 16;
+    if (off + 16 <= n) {
+        *(uint4*)(dst + base + off) = *(const uint4*)(src + base + off);
+    } else if (off < n) {
+        // The one lane holding the value's sub-16 B tail
+        for (u32 i = off; i < n; i++) {
+            dst[base + i] = src[base + i];
+        }
+    }
+}
+
 inline u32 gridFor(u64 items)
 {
     // One element per lane, uncapped: a 2048-block grid-stride copy
@@ -711,6 +748,34 @@ hipError_t famGatherPages(const void* payloadDev,
                        pageIdxDev,
                        (uint4*)outDev,
                        nDirty);
+    return hipGetLastError();
+}
+
+hipError_t famCommitPages(const void* srcHostMapped,
+                          void* dstDev,
+                          const uint32_t* pageIdx,
+                          uint32_t nPages,
+                          uint64_t valueBytes,
+                          hipStream_t stream)
+{
+    if (nPages == 0) {
+        return hipSuccess;
+    }
+    // Page offsets keep the 16 B lane accesses aligned only from
+    // 16 B-aligned bases
+    if ((((uintptr_t)srcHostMapped | (uintptr_t)dstDev) & 15) != 0) {
+        return hipErrorInvalidValue;
+    }
+    hipLaunchKernelGGL(famKvCommitPagesKernel,
+                       dim3(nPages),
+                       dim3(FAM_KERNEL_BLOCK),
+                       0,
+                       stream,
+                       (const u8*)srcHostMapped,
+                       (u8*)dstDev,
+                       pageIdx,
+                       nPages,
+                       valueBytes);
     return hipGetLastError();
 }
 

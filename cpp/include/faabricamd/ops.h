@@ -76,6 +76,17 @@ hipError_t famGatherPages(const void* payloadDev,
                           void* outDev,
                           uint32_t nDirty,
                           hipStream_t stream);
+// State-KV mirror commit (famKvCommitPagesKernel): copy the listed 4 KiB
+// pages of a pinned host mirror to the same offsets of the HBM value,
+// one block per page. srcHostMapped and pageIdx are device-visible
+// pointers to pinned host memory (hipHostGetDevicePointer); the value's
+// partial last page is copied to the byte.
+hipError_t famCommitPages(const void* srcHostMapped,
+                          void* dstDev,
+                          const uint32_t* pageIdx,
+                          uint32_t nPages,
+                          uint64_t valueBytes,
+                          hipStream_t stream);
 hipError_t famElementwiseOp(void* inout,
                             const void* in,
                             uint64_t count,

@@ -45,6 +45,22 @@ enum class StateCalls : uint8_t
     Unlock = 11,
 };
 
+// Sweep a page-dirty bitmap (bit p of word p/64 = page p) covering nPages
+// pages: every word is taken with exchange(0), the set bits below nPages
+// are written to out in ascending order (out has room for nPages
+// entries). Returns the number written; the bitmap is left all zero.
+size_t kvSweepDirtyBitmap(std::atomic<uint64_t>* words,
+                          size_t nPages,
+                          uint32_t* out);
+
+// Process-wide device-KV commit counters (observability + tests)
+struct KvCommitStats
+{
+    uint64_t launches = 0; // famCommitPages kernel launches
+    uint64_t pages = 0;    // pages those launches listed
+};
+KvCommitStats kvCommitStats();
+
 class StateKeyValue
 {
   public:
@@ -119,39 +135,41 @@ class StateKeyValue
     int device = 0;
     uint8_t* devPtr = nullptr;
 
-    // Pinned host mirror for device values (group-commit write-through):
-    // chunk writes memcpy into the mirror and enqueue an async H2D on a
-    // stripe stream with NO per-op sync — the ~12 us host-visible
-    // latency of a synchronous 4 KiB HIP copy was the measured floor of
-    // the batch path (BASELINE.md config-5 history). Reads are served
-    // from the mirror (filled D2H on first touch). sync() is the
-    // durability point; direct devPtr uses flush/invalidate around it.
+    // Pinned host mirror for device values (deferred group commit):
+    // a chunk write memcpys into the mirror and sets the page's bit in
+    // an atomic dirty bitmap — no HIP call on the write path at all
+    // (one 4 KiB blit per write measured ~5-6 us of serialised GPU time
+    // each and convoyed on the HIP driver lock under 128-thread
+    // batches). Reads are served from the mirror (filled D2H on first
+    // touch). sync() is the durability point: it sweeps the bitmap into
+    // a pinned page list and commits every listed page with ONE scatter
+    // kernel (famCommitPages) reading the mirror in place over the host
+    // link, then synchronises once. Direct devPtr uses sync/invalidate
+    // around themselves.
     //
-    // The mirror is STRIPED: the value is split into 64 KiB blocks
-    // round-robined over KV_STRIPES (mutex, HIP stream) pairs so
-    // concurrent executors touching different ranges never serialise on
-    // one lock or one stream (128 concurrent kvtouch functions measured
-    // ~228 us of thread-time each on the single-mutex design). Per-range
-    // ordering holds because every byte maps to exactly one stripe.
+    // Host-side exclusion is STRIPED: the value is split into 64 KiB
+    // blocks round-robined over KV_STRIPES mutexes so concurrent
+    // executors touching different ranges never serialise on one lock
+    // (128 concurrent kvtouch functions measured ~228 us of thread-time
+    // each on the single-mutex design). sync() takes no stripe mutex: a
+    // page rewritten while the commit kernel reads it has its bit set
+    // again by its writer (after the memcpy) and is committed by the
+    // next sync().
   public:
     static constexpr int KV_STRIPES = 16;
 
   private:
     static constexpr uint64_t KV_STRIPE_BLOCK = 64 * 1024;
-    // Stripes (mutex + HIP stream) live in one PROCESS-GLOBAL pool
-    // shared by every KV: per-KV stream sets measured ~1 MiB+ of HBM
-    // settle per stream. Ordering still holds — every (kv, byte) maps
-    // to exactly one stripe.
-    bool stripesReady = false;
+    // Stripe mutexes live in one PROCESS-GLOBAL pool shared by every
+    // KV, as do the commit stream and its page-list buffer (guarded by
+    // one commit mutex; lock order is stripe -> commit)
     std::mutex mirrorMx; // guards mirror bring-up only
     uint8_t* mirror = nullptr;
+    uint8_t* mirrorDev = nullptr;  // device-visible address of mirror
     std::vector<char> mirrorValid; // per 4 KiB page (owned by its stripe)
-    // Write-back dirty pages: writes memcpy into the mirror and mark
-    // here; sync() coalesces dirty runs into few H2D enqueues (per-op
-    // write-through enqueues convoyed on the HIP driver lock under
-    // 128-thread batches)
-    std::vector<char> mirrorDirty;
-    std::atomic<bool> mirrorAnyDirty{ false };
+    // One bit per 4 KiB page, set (release) after the page's memcpy
+    std::unique_ptr<std::atomic<uint64_t>[]> mirrorDirty;
+    size_t mirrorDirtyWords = 0;
     bool mirrorFailed = false;
     bool mirrorUsable();
     // Runtime-capped stripe count (FAABRIC_KV_STRIPES, default 16)
@@ -160,12 +178,22 @@ class StateKeyValue
     // per subrange with that stripe's lock held
     template<typename Fn>
     void forEachStripeRange(uint64_t offset, size_t len, Fn&& fn);
-    void mirrorFillLocked(int stripe, uint64_t offset, size_t len);
+    void mirrorFillLocked(uint64_t offset, size_t len);
     void mirrorInvalidate(uint64_t offset, size_t len);
+    // Commit mutex held: sweep the dirty bitmap into list (room for
+    // every page of this value) and launch the commit kernel over it;
+    // returns the number of pages enqueued
+    uint32_t commitEnqueueLocked(uint32_t* list);
+    size_t mirrorPages() const { return mirrorValid.size(); }
 
   public:
-    // Drain pending device writes (group-commit durability point)
+    // Commit pending mirror writes to HBM (group-commit durability
+    // point): at most one kernel launch and one stream synchronise, no
+    // HIP call when nothing is dirty
     void sync();
+    // sync() for a set of KVs: one launch per dirty KV, one synchronise
+    static void syncMany(
+      const std::vector<std::shared_ptr<StateKeyValue>>& kvs);
 
   private:
 

@@ -5,6 +5,7 @@
 #include "faabricamd/ops.h"
 #include "faabricamd/ptp.h"
 #include "faabricamd/util.h"
+#include "faabricamd/utilextras.h"
 
 #include <hip/hip_runtime.h>
 
@@ -18,36 +19,91 @@ static std::string kvKeyOf(const std::string& user, const std::string& key)
     return user + "/" + key;
 }
 
-struct MirrorStripe
-{
-    std::mutex mx;
-    void* stream = nullptr;
-};
+// Process-global stripe mutex pool shared by all device KVs (host-side
+// exclusion between chunk readers/writers of the same 64 KiB block)
+static std::mutex gStripeMx[StateKeyValue::KV_STRIPES];
 
-// Process-global stripe pool shared by all device KVs
-static MirrorStripe gStripes[StateKeyValue::KV_STRIPES];
-static std::mutex gStripesMx;
-static bool gStripesReady = false;
+// Process-global commit plane: ONE stream and ONE pinned page-list buffer
+// (grown on demand) serve every KV's sync(); gCommitMx is held from the
+// bitmap sweep until the stream has drained, so at most one commit (or
+// mirror fill) is in flight per process. Lock order: stripe -> commit.
+static std::mutex gCommitMx;
+static hipStream_t gCommitStream = nullptr;
+static uint32_t* gCommitList = nullptr;    // pinned host
+static uint32_t* gCommitListDev = nullptr; // its device-visible address
+static size_t gCommitListCap = 0;          // entries
+static std::atomic<uint64_t> gCommitLaunches{ 0 };
+static std::atomic<uint64_t> gCommitPages{ 0 };
 
-static bool ensureGlobalStripes(int device)
+KvCommitStats kvCommitStats()
 {
-    std::lock_guard<std::mutex> lock(gStripesMx);
-    if (gStripesReady) {
+    KvCommitStats s;
+    s.launches = gCommitLaunches.load(std::memory_order_relaxed);
+    s.pages = gCommitPages.load(std::memory_order_relaxed);
+    return s;
+}
+
+size_t kvSweepDirtyBitmap(std::atomic<uint64_t>* words,
+                          size_t nPages,
+                          uint32_t* out)
+{
+    size_t nWords = (nPages + 63) / 64;
+    size_t n = 0;
+    for (size_t w = 0; w < nWords; w++) {
+        // Skip clean words without the RMW (the common case)
+        if (words[w].load(std::memory_order_relaxed) == 0) {
+            continue;
+        }
+        uint64_t bits = words[w].exchange(0, std::memory_order_acquire);
+        while (bits != 0) {
+            size_t page = w * 64 + (size_t)__builtin_ctzll(bits);
+            bits &= bits - 1;
+            if (page < nPages) {
+                out[n++] = (uint32_t)page;
+            }
+        }
+    }
+    return n;
+}
+
+// Commit mutex held
+static bool ensureCommitStreamLocked(int device)
+{
+    if (gCommitStream != nullptr) {
         return true;
     }
     (void)hipSetDevice(device);
-    for (int i = 0; i < StateKeyValue::KV_STRIPES; i++) {
-        if (gStripes[i].stream == nullptr) {
-            hipStream_t st = nullptr;
-            if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) !=
-                hipSuccess) {
-                return false;
-            }
-            gStripes[i].stream = (void*)st;
-        }
+    hipStream_t st = nullptr;
+    if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) {
+        return false;
     }
-    gStripesReady = true;
+    gCommitStream = st;
     return true;
+}
+
+// Commit mutex held, commit stream idle (nothing reads the old buffer)
+static void ensureCommitListLocked(size_t entries)
+{
+    if (entries <= gCommitListCap) {
+        return;
+    }
+    size_t cap = std::max<size_t>(gCommitListCap * 2, 1024);
+    while (cap < entries) {
+        cap *= 2;
+    }
+    void* pinned = nullptr;
+    void* dev = nullptr;
+    if (hipHostMalloc(&pinned, cap * sizeof(uint32_t),
+                      hipHostMallocDefault) != hipSuccess ||
+        hipHostGetDevicePointer(&dev, pinned, 0) != hipSuccess) {
+        throw FaabricException("pinned alloc for KV commit list failed");
+    }
+    if (gCommitList != nullptr) {
+        (void)hipHostFree(gCommitList);
+    }
+    gCommitList = (uint32_t*)pinned;
+    gCommitListDev = (uint32_t*)dev;
+    gCommitListCap = cap;
 }
 
 StateKeyValue::StateKeyValue(std::string userIn,
@@ -74,7 +130,13 @@ StateKeyValue::StateKeyValue(std::string userIn,
             hipMalloc(&devPtr, valueSize) != hipSuccess) {
             throw FaabricException("HBM alloc for state KV failed");
         }
-        hipMemset(devPtr, 0, valueSize);
+        // The memset is asynchronous on the null stream and the commit
+        // stream does not wait for it: finish it here, or it can land
+        // on top of the value's first committed pages
+        if (hipMemset(devPtr, 0, valueSize) != hipSuccess ||
+            hipStreamSynchronize(nullptr) != hipSuccess) {
+            throw FaabricException("HBM clear for state KV failed");
+        }
     } else {
         value.resize(valueSize, 0);
     }
@@ -85,15 +147,14 @@ StateKeyValue::StateKeyValue(std::string userIn,
 
 StateKeyValue::~StateKeyValue()
 {
-    if (stripesReady) {
-        // Streams are process-global; just drain writes targeting our
-        // HBM before it is freed
-        for (int s = 0; s < KV_STRIPES; s++) {
-            std::lock_guard<std::mutex> lock(gStripes[s].mx);
-            (void)hipStreamSynchronize((hipStream_t)gStripes[s].stream);
-        }
-    }
     if (mirror != nullptr) {
+        // The commit stream is process-global; drain anything reading
+        // our mirror or writing our HBM before either is freed
+        std::lock_guard<std::mutex> lock(gCommitMx);
+        if (gCommitStream != nullptr) {
+            (void)hipSetDevice(device);
+            (void)hipStreamSynchronize(gCommitStream);
+        }
         (void)hipHostFree(mirror);
     }
     if (devPtr != nullptr) {
@@ -129,20 +190,33 @@ bool StateKeyValue::mirrorUsable()
         return false;
     }
     void* pinned = nullptr;
+    void* pinnedDev = nullptr;
     if (hipSetDevice(device) != hipSuccess ||
         hipHostMalloc(&pinned, valueSize, hipHostMallocDefault) !=
           hipSuccess) {
         mirrorFailed = true;
         return false;
     }
-    if (!ensureGlobalStripes(device)) {
+    bool streamOk = false;
+    {
+        std::lock_guard<std::mutex> commitLock(gCommitMx);
+        streamOk = ensureCommitStreamLocked(device);
+    }
+    if (!streamOk ||
+        hipHostGetDevicePointer(&pinnedDev, pinned, 0) != hipSuccess) {
         (void)hipHostFree(pinned);
         mirrorFailed = true;
         return false;
     }
-    mirrorValid.assign((valueSize + MIRROR_PAGE - 1) / MIRROR_PAGE, 0);
-    mirrorDirty.assign(mirrorValid.size(), 0);
-    stripesReady = true;
+    size_t nPages = (valueSize + MIRROR_PAGE - 1) / MIRROR_PAGE;
+    mirrorValid.assign(nPages, 0);
+    mirrorDirtyWords = (nPages + 63) / 64;
+    mirrorDirty =
+      std::make_unique<std::atomic<uint64_t>[]>(mirrorDirtyWords);
+    for (size_t w = 0; w < mirrorDirtyWords; w++) {
+        mirrorDirty[w].store(0, std::memory_order_relaxed);
+    }
+    mirrorDev = (uint8_t*)pinnedDev;
     mirror = (uint8_t*)pinned;
     return true;
 }
@@ -156,14 +230,13 @@ void StateKeyValue::forEachStripeRange(uint64_t offset, size_t len, Fn&& fn)
         uint64_t blockEnd =
           (pos / KV_STRIPE_BLOCK + 1) * KV_STRIPE_BLOCK;
         uint64_t n = std::min(end, blockEnd) - pos;
-        int s = stripeOf(pos);
-        std::lock_guard<std::mutex> lock(gStripes[s].mx);
-        fn(s, pos, (size_t)n);
+        std::lock_guard<std::mutex> lock(gStripeMx[stripeOf(pos)]);
+        fn(pos, (size_t)n);
         pos += n;
     }
 }
 
-// Runtime stripe count (1..KV_STRIPES) for A/B measurement
+// Runtime stripe (lock) count (1..KV_STRIPES) for A/B measurement
 static int kvStripeCount()
 {
     static const int v = []() {
@@ -187,17 +260,27 @@ int StateKeyValue::stripeOf(uint64_t offset) const
     return (int)((salt + offset / KV_STRIPE_BLOCK) % kvStripeCount());
 }
 
-void StateKeyValue::mirrorFillLocked(int stripe,
-                                     uint64_t offset,
-                                     size_t len)
+void StateKeyValue::mirrorFillLocked(uint64_t offset, size_t len)
 {
-    // Caller holds the stripe's mutex; [offset, +len) lies inside this
-    // stripe's block. Fill whole stale pages. The D2H rides the stripe
-    // stream, so it is ordered after that range's pending H2Ds.
+    // Caller holds the range's stripe mutex; [offset, +len) lies inside
+    // one stripe block. Fill whole stale pages. A stale page is never
+    // dirty (invalidation clears both), and the D2H runs on the commit
+    // stream under the commit mutex, so it cannot overtake a commit.
     size_t firstPage = offset / MIRROR_PAGE;
     size_t lastPage = (offset + len - 1) / MIRROR_PAGE;
+    bool anyStale = false;
+    for (size_t p = firstPage; p <= lastPage; p++) {
+        if (mirrorValid[p] == 0) {
+            anyStale = true;
+            break;
+        }
+    }
+    if (!anyStale) {
+        return;
+    }
+    std::lock_guard<std::mutex> commitLock(gCommitMx);
+    (void)hipSetDevice(device);
     size_t run = 0;
-    bool filled = false;
     for (size_t p = firstPage; p <= lastPage + 1; p++) {
         bool stale = p <= lastPage && mirrorValid[p] == 0;
         if (stale) {
@@ -208,18 +291,14 @@ void StateKeyValue::mirrorFillLocked(int stripe,
             size_t start = (p - run) * MIRROR_PAGE;
             size_t n = std::min(run * MIRROR_PAGE, valueSize - start);
             (void)hipMemcpyAsync(mirror + start, devPtr + start, n,
-                                 hipMemcpyDeviceToHost,
-                                 (hipStream_t)gStripes[stripe].stream);
+                                 hipMemcpyDeviceToHost, gCommitStream);
             for (size_t q = p - run; q < p; q++) {
                 mirrorValid[q] = 1;
             }
-            filled = true;
             run = 0;
         }
     }
-    if (filled) {
-        (void)hipStreamSynchronize((hipStream_t)gStripes[stripe].stream);
-    }
+    (void)hipStreamSynchronize(gCommitStream);
 }
 
 void StateKeyValue::mirrorInvalidate(uint64_t offset, size_t len)
@@ -227,8 +306,7 @@ void StateKeyValue::mirrorInvalidate(uint64_t offset, size_t len)
     if (mirror == nullptr || len == 0) {
         return;
     }
-    forEachStripeRange(offset, len, [&](int s, uint64_t o, size_t n) {
-        (void)s;
+    forEachStripeRange(offset, len, [&](uint64_t o, size_t n) {
         size_t firstPage = o / MIRROR_PAGE;
         size_t lastPage = (o + n - 1) / MIRROR_PAGE;
         for (size_t p = firstPage;
@@ -236,9 +314,34 @@ void StateKeyValue::mirrorInvalidate(uint64_t offset, size_t len)
             mirrorValid[p] = 0;
             // Direct-HBM landings are ordered after sync(); any dirty
             // bit left here belongs to a write the landing overwrote
-            mirrorDirty[p] = 0;
+            mirrorDirty[p / 64].fetch_and(~(1ULL << (p % 64)),
+                                          std::memory_order_acq_rel);
         }
     });
+}
+
+uint32_t StateKeyValue::commitEnqueueLocked(uint32_t* list)
+{
+    size_t n = kvSweepDirtyBitmap(mirrorDirty.get(), mirrorPages(), list);
+    if (n == 0) {
+        return 0;
+    }
+    (void)hipSetDevice(device);
+    const uint32_t* listDev = gCommitListDev + (list - gCommitList);
+    hipError_t err = famCommitPages(mirrorDev, devPtr, listDev,
+                                    (uint32_t)n, valueSize, gCommitStream);
+    if (err != hipSuccess) {
+        // Put the pages back so a later sync() retries them
+        for (size_t i = 0; i < n; i++) {
+            mirrorDirty[list[i] / 64].fetch_or(1ULL << (list[i] % 64),
+                                               std::memory_order_release);
+        }
+        throw FaabricException(std::string("KV commit launch failed: ") +
+                               hipGetErrorString(err));
+    }
+    gCommitLaunches.fetch_add(1, std::memory_order_relaxed);
+    gCommitPages.fetch_add(n, std::memory_order_relaxed);
+    return (uint32_t)n;
 }
 
 void StateKeyValue::sync()
@@ -246,41 +349,55 @@ void StateKeyValue::sync()
     if (mirror == nullptr) {
         return;
     }
-    if (mirrorAnyDirty.exchange(false, std::memory_order_acq_rel)) {
-        (void)hipSetDevice(device);
-        // Coalesce dirty pages into maximal runs; each run is enqueued
-        // per stripe block under that stripe's lock (mutual exclusion
-        // with writers keeps the page content consistent). Pages
-        // dirtied concurrently re-set the flag and are committed by
-        // their writer's own sync.
-        size_t nPages = mirrorDirty.size();
-        size_t p = 0;
-        while (p < nPages) {
-            if (mirrorDirty[p] == 0) {
-                p++;
-                continue;
-            }
-            size_t q = p;
-            while (q < nPages && mirrorDirty[q] != 0) {
-                mirrorDirty[q] = 0;
-                q++;
-            }
-            uint64_t start = (uint64_t)p * MIRROR_PAGE;
-            size_t len =
-              std::min<uint64_t>((uint64_t)q * MIRROR_PAGE, valueSize) -
-              start;
-            forEachStripeRange(start, len, [&](int s, uint64_t o,
-                                               size_t n) {
-                (void)hipMemcpyAsync(devPtr + o, mirror + o, n,
-                                     hipMemcpyHostToDevice,
-                                     (hipStream_t)gStripes[s].stream);
-            });
-            p = q;
+    // Taken even when nothing of ours is dirty: a concurrent sync() may
+    // have swept our bits and still be in flight, and returning before
+    // it drains would not be a durability point
+    std::lock_guard<std::mutex> lock(gCommitMx);
+    ensureCommitListLocked(mirrorPages());
+    if (commitEnqueueLocked(gCommitList) == 0) {
+        return;
+    }
+    if (hipStreamSynchronize(gCommitStream) != hipSuccess) {
+        throw FaabricException("KV commit failed on the device");
+    }
+}
+
+void StateKeyValue::syncMany(
+  const std::vector<std::shared_ptr<StateKeyValue>>& kvs)
+{
+    std::lock_guard<std::mutex> lock(gCommitMx);
+    size_t total = 0;
+    for (auto& kv : kvs) {
+        if (kv->mirror != nullptr) {
+            total += kv->mirrorPages();
         }
     }
-    for (int s = 0; s < KV_STRIPES; s++) {
-        std::lock_guard<std::mutex> lock(gStripes[s].mx);
-        (void)hipStreamSynchronize((hipStream_t)gStripes[s].stream);
+    if (total == 0) {
+        return;
+    }
+    ensureCommitListLocked(total);
+    // Each KV's page list takes its own segment of the buffer: the
+    // kernels read the lists in place until the one synchronise below
+    size_t used = 0;
+    bool launched = false;
+    for (auto& kv : kvs) {
+        if (kv->mirror == nullptr) {
+            continue;
+        }
+        uint32_t n = 0;
+        try {
+            n = kv->commitEnqueueLocked(gCommitList + used);
+        } catch (...) {
+            if (launched) {
+                (void)hipStreamSynchronize(gCommitStream);
+            }
+            throw;
+        }
+        used += n;
+        launched = launched || n > 0;
+    }
+    if (launched && hipStreamSynchronize(gCommitStream) != hipSuccess) {
+        throw FaabricException("KV commit failed on the device");
     }
 }
 
@@ -300,20 +417,6 @@ static hipStream_t threadCopyStream()
     return stream;
 }
 
-// Write policy, measured same-box (profiles/kv_writeback_ab.json):
-// write-through (default) enqueues one H2D per op from the worker
-// thread that did the write — the enqueues overlap batch execution.
-// Write-back (=1) marks pages dirty and coalesces H2Ds at sync(), but
-// that serializes the whole flush on the sync caller's critical path:
-// 23% slower at 128-function batches. Kept as a knob because the
-// trade flips for workloads with many tiny writes and rare syncs.
-static bool kvWriteBack()
-{
-    static const bool v =
-      getEnvVarInt("FAABRIC_KV_WRITEBACK", 0) != 0;
-    return v;
-}
-
 static bool kvAsyncCopy()
 {
     static bool v = getEnvVarInt("FAABRIC_KV_ASYNC_COPY", 0) != 0;
@@ -324,12 +427,11 @@ void StateKeyValue::readLocal(uint64_t offset, uint8_t* out, size_t len)
 {
     if (onDevice) {
         if (mirrorUsable()) {
-            (void)hipSetDevice(device);
-            forEachStripeRange(
-              offset, len, [&](int s, uint64_t o, size_t n) {
-                  mirrorFillLocked(s, o, n); // no-op when pages valid
-                  std::memcpy(out + (o - offset), mirror + o, n);
-              });
+            // Mirror hit: no HIP call (a fill sets its own device)
+            forEachStripeRange(offset, len, [&](uint64_t o, size_t n) {
+                mirrorFillLocked(o, n); // no-op when pages valid
+                std::memcpy(out + (o - offset), mirror + o, n);
+            });
             return;
         }
         (void)hipSetDevice(device);
@@ -353,13 +455,13 @@ void StateKeyValue::writeLocal(uint64_t offset,
 {
     if (onDevice) {
         if (mirrorUsable()) {
-            // Group-commit write-back: memcpy into the pinned mirror and
-            // mark the pages dirty; sync() (the durability point)
-            // coalesces dirty runs into few H2D enqueues. Reads serve
-            // from the mirror, so they always see the newest bytes.
-            (void)hipSetDevice(device);
+            // Deferred group commit: memcpy into the pinned mirror and
+            // set the pages' dirty bits; sync() (the durability point)
+            // commits all dirty pages with one scatter kernel. No HIP
+            // call here. Reads serve from the mirror, so they always
+            // see the newest bytes.
             forEachStripeRange(
-              offset, len, [&](int s, uint64_t o, size_t n) {
+              offset, len, [&](uint64_t o, size_t n) {
                   // A partially-written invalid boundary page must be
                   // filled from HBM first, or its untouched bytes would
                   // read stale
@@ -373,32 +475,27 @@ void StateKeyValue::writeLocal(uint64_t offset,
                   };
                   if (mirrorValid[firstPage] == 0 &&
                       !coversPage(firstPage)) {
-                      mirrorFillLocked(s, firstPage * MIRROR_PAGE, 1);
+                      mirrorFillLocked(firstPage * MIRROR_PAGE, 1);
                   }
                   if (lastPage != firstPage &&
                       mirrorValid[lastPage] == 0 &&
                       !coversPage(lastPage)) {
-                      mirrorFillLocked(s, lastPage * MIRROR_PAGE, 1);
+                      mirrorFillLocked(lastPage * MIRROR_PAGE, 1);
                   }
                   std::memcpy(mirror + o, data + (o - offset), n);
-                  if (kvWriteBack()) {
-                      for (size_t p = firstPage; p <= lastPage; p++) {
+                  // Dirty bits go up AFTER the bytes: a commit that
+                  // read the page mid-memcpy is redone by the next sync
+                  for (size_t p = firstPage; p <= lastPage;) {
+                      size_t w = p / 64;
+                      uint64_t bits = 0;
+                      for (; p <= lastPage && p / 64 == w; p++) {
                           mirrorValid[p] = 1;
-                          mirrorDirty[p] = 1;
+                          bits |= 1ULL << (p % 64);
                       }
-                  } else {
-                      for (size_t p = firstPage; p <= lastPage; p++) {
-                          mirrorValid[p] = 1;
-                      }
-                      (void)hipMemcpyAsync(
-                        devPtr + o, mirror + o, n,
-                        hipMemcpyHostToDevice,
-                        (hipStream_t)gStripes[s].stream);
+                      mirrorDirty[w].fetch_or(bits,
+                                              std::memory_order_release);
                   }
               });
-            if (kvWriteBack()) {
-                mirrorAnyDirty.store(true, std::memory_order_release);
-            }
             return;
         }
         (void)hipSetDevice(device);
@@ -1041,9 +1138,14 @@ void State::syncAll()
             kvs.push_back(kv);
         }
     }
-    for (auto& kv : kvs) {
-        kv->sync();
+    PROF_START(kv_sync)
+    try {
+        StateKeyValue::syncMany(kvs);
+    } catch (...) {
+        PROF_END(kv_sync)
+        throw;
     }
+    PROF_END(kv_sync)
 }
 
 void State::forceClearAll(bool global)

@@ -46,6 +46,9 @@ def main():
         ber = _core.batch_exec_factory("bench", "kvtouch", batch)
         _core.call_functions(ber)
         wait_for_batch(ber.app_id, batch, 30_000)
+        # Durability point: without it the writes stay in the pinned
+        # mirror and the device commit path is never exercised
+        _core.state_sync_all()
         n += 1
         if rmid is None and time.time() - t0 > 0.6 * seconds:
             rmid = rss_mb()

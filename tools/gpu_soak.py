@@ -68,8 +68,8 @@ def main(cycles=25):
         rs = wait_for_batch(ber.app_id, 1, 60_000)
         assert rs[0].return_value == 0, rs[0].output_data
 
-        # 2. HBM KV churn (pinned-mirror write-through path: partial
-        # writes, mirror fills, group-commit sync)
+        # 2. HBM KV churn (pinned-mirror deferred-commit path: partial
+        # writes, mirror fills, one commit kernel per sync)
         kv = _core.state_get_kv_device("gsoak", f"k{i % 3}", 1 << 20)
         kv.set(bytes([i % 251]) * (1 << 20))
         assert kv.get_chunk(0, 1) == bytes([i % 251])
