@@ -96,7 +96,22 @@ tsan-dist:
 	DISTTEST_BASE_OFFSET=6400 DISTTEST_STOP_FILE=$(BUILD)/tsan/stop \
 	    TSAN_OPTIONS="report_bugs=1" $(BUILD)/tsan/disttest
 
-.PHONY: asan-check tsan-check asan-dist tsan-dist
+# Dispatch hand-off primitives (mailbox + idle list) on their own: a
+# header-only, host-only stress program, so the sanitizers see just them
+stress-tsan:
+	@mkdir -p $(BUILD)/tsan
+	$(HIPCC) -O1 -g -std=c++20 -fsanitize=thread -Icpp/include \
+	    examples/dispatch_stress.cpp -pthread -o $(BUILD)/tsan/dispatch_stress
+	TSAN_OPTIONS="report_bugs=1 halt_on_error=1" $(BUILD)/tsan/dispatch_stress
+
+stress-asan:
+	@mkdir -p $(BUILD)/asan
+	$(HIPCC) -O1 -g -std=c++20 -fsanitize=address,undefined \
+	    -fno-omit-frame-pointer -Icpp/include \
+	    examples/dispatch_stress.cpp -pthread -o $(BUILD)/asan/dispatch_stress
+	UBSAN_OPTIONS="halt_on_error=1" $(BUILD)/asan/dispatch_stress
+
+.PHONY: asan-check tsan-check asan-dist tsan-dist stress-tsan stress-asan
 
 $(BUILD)/%: $(BUILD)/examples/%.o $(CORE_OBJS)
 	$(HIPCC) $< $(CORE_OBJS) \

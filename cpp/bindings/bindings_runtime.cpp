@@ -902,6 +902,26 @@ void initRuntimeBindings(py::module_& m)
         d["decision_cache"] = DecisionCache::get().size();
         return d;
     });
+    // Dispatch-path bookkeeping: idle-list entries over all warm pools,
+    // apps with a planner message index, slots the planner counts as used
+    m.def("_debug_dispatch_sizes", [] {
+        py::dict d;
+        d["idle_executors"] = Scheduler::get().debugIdleCount();
+        d["planner_msg_index_apps"] = Planner::get().debugMsgIndexCount();
+        d["planner_used_slots"] = Planner::get().debugUsedSlots();
+        return d;
+    });
+    // Id of the executor running the calling function
+    m.def("_debug_current_executor_id", [] {
+        return ExecutorContext::get().getExecutor()->id;
+    });
+    // Report `msg` as a result through the planner client, as an executor
+    // does (used to deliver a result a second time)
+    m.def("_debug_set_message_result", [](const Message& msg) {
+        auto copy = std::make_shared<Message>(msg);
+        py::gil_scoped_release release;
+        getPlannerClient().setMessageResult(copy);
+    });
     // Device-KV commit counters: famCommitPages launches / pages listed
     m.def("_debug_kv_commit_stats", [] {
         KvCommitStats s = kvCommitStats();

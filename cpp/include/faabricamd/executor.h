@@ -21,6 +21,7 @@
 #include <thread>
 #include <vector>
 
+#include "faabricamd/mailbox.h"
 #include "faabricamd/messages.h"
 #include "faabricamd/queue.h"
 #include "faabricamd/dirty.h"
@@ -89,17 +90,29 @@ struct ExecutorTask
     int msgIdx = 0;
     std::shared_ptr<BatchExecuteRequest> req;
     bool stop = false;
+    // The only task of its executor's batch: completing it ends the
+    // batch, no shared counter involved
+    bool single = false;
+    // Stamped at hand-off when FAABRIC_PROF is on (exec_wake scope)
+    int64_t enqueueNs = 0;
 };
 
-class Executor
+class Executor : public std::enable_shared_from_this<Executor>
 {
   public:
     explicit Executor(Message& msg);
     virtual ~Executor();
 
     // Dispatch tasks to the pool (reference: src/executor/Executor.cpp:111)
-    void executeTasks(std::vector<int> msgIdxs,
-                      std::shared_ptr<BatchExecuteRequest> req);
+    void executeTasks(const std::vector<int>& msgIdxs,
+                      const std::shared_ptr<BatchExecuteRequest>& req);
+    // One message of a FUNCTIONS batch on this executor: the common case
+    // of the batch path. Without a snapshot to restore it hands the task
+    // to pool thread 0 with one mailbox post: no counter allocation, no
+    // index vector, no lock once that thread runs. Anything else goes
+    // through executeTasks.
+    void executeSingleTask(int msgIdx,
+                           const std::shared_ptr<BatchExecuteRequest>& req);
 
     // Fork-join THREADS batch over a shared memory snapshot (reference:
     // Executor::executeThreads; call stack SURVEY §3.4). Must be called
@@ -135,6 +148,13 @@ class Executor
     void claim();
     void releaseClaim();
     bool isClaimed() const { return claimed.load(); }
+    // The warm pool's idle list; every releaseClaim() pushes this executor
+    // onto it (set once by the scheduler, before the first task)
+    using IdleExecutors = IdleList<std::shared_ptr<Executor>>;
+    void setIdleList(std::shared_ptr<IdleExecutors> list)
+    {
+        idleList = std::move(list);
+    }
 
     long getMillisSinceLastExec() const;
     void shutdown();
@@ -159,9 +179,19 @@ class Executor
                           bool isLastInBatch);
 
     int threadPoolSize = 0;
-    std::vector<std::shared_ptr<Queue<ExecutorTask>>> threadTaskQueues;
+    // One mailbox per started pool thread, created with the thread under
+    // threadsMx. poolThreadUp[i] is set once both exist, so the hand-off
+    // can skip the lock for a running thread.
+    using TaskMailbox = Mailbox<ExecutorTask>;
+    std::vector<std::unique_ptr<TaskMailbox>> threadMailboxes;
     std::vector<std::thread> threadPoolThreads;
+    std::unique_ptr<std::atomic<bool>[]> poolThreadUp;
     std::mutex threadsMx;
+    // Caller holds threadsMx
+    void ensurePoolThreadLocked(int poolIdx);
+    void postTask(int poolIdx, ExecutorTask&& task);
+
+    std::shared_ptr<IdleExecutors> idleList;
 
     std::atomic<bool> claimed{ false };
     std::atomic<int64_t> lastExecMs{ 0 };

@@ -13,6 +13,7 @@
 #include <set>
 #include <shared_mutex>
 #include <thread>
+#include <unordered_map>
 #include <vector>
 
 #include "faabricamd/messages.h"
@@ -62,6 +63,14 @@ struct PlannerState
 {
     std::map<std::string, std::shared_ptr<PlannerHost>> hostMap;
     InFlightReqs inFlightReqs;
+    // appId → message id → position in the in-flight request's `messages`
+    // (the decision's parallel vectors keep the same positions). Built on
+    // the app's first result and kept across each swap-and-pop, so a
+    // result is found in O(1). Every use checks the position against the
+    // message id and rebuilds the app's index on a mismatch, which is all
+    // SCALE_CHANGE appends, DIST_CHANGE copies and un-freezes need.
+    std::unordered_map<int32_t, std::unordered_map<int32_t, uint32_t>>
+      inFlightMsgPos;
     std::map<int32_t, std::shared_ptr<SchedulingDecision>>
       preloadedSchedulingDecisions;
     // appId → msgId → result
@@ -102,6 +111,8 @@ class Planner
     size_t debugAppResultsCount();
     size_t debugDoneAppsCount();
     size_t debugInFlightCount();
+    size_t debugMsgIndexCount();
+    int debugUsedSlots();
 
     // Returns true if the app is already complete (or unknown); else
     // records host for a BATCH_DONE push on completion
@@ -143,6 +154,10 @@ class Planner
 
   private:
     void purgeOldResultsLocked();
+    // Position of msgId in req.messages through the app's index, or -1
+    int64_t findInFlightPosLocked(int32_t appId,
+                                  const BatchExecuteRequest& req,
+                                  int32_t msgId);
     void setMessageResultLocked(
       const std::shared_ptr<Message>& msg,
       std::vector<std::pair<std::string, std::shared_ptr<Message>>>& waiters,

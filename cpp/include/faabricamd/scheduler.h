@@ -60,24 +60,38 @@ class Scheduler
     void clearRecordedMessages();
 
     size_t getExecutorCount();
+    // Idle-list entries over all warm pools (stale ones included)
+    size_t debugIdleCount();
 
   private:
     Scheduler();
 
-    std::shared_ptr<Executor> claimExecutor(Message& msg);
-
-    // Claims take the lock SHARED (concurrent tryClaim CAS scans from
-    // the dispatcher threads — a plain mutex here measured ~41 us of
-    // wall per claim from contention at 8 dispatchers x 128 messages);
-    // executor creation and reaping take it unique.
-    std::shared_mutex schedMx;
     struct WarmPool
     {
+        // Every executor of one function, claimed or not
         std::vector<std::shared_ptr<Executor>> list;
-        // Rotating claim hint: first-fit from index 0 costs O(N^2)
-        // probes per N-message batch; rotating makes it ~O(1)
-        std::atomic<size_t> hint{ 0 };
+        // The unclaimed ones: Executor::releaseClaim pushes, claims pop in
+        // O(1). A hint only: Executor::tryClaim decides ownership, so a
+        // stale entry is dropped and can never cause a double claim.
+        // Shared with the executors, which may outlive the pool.
+        std::shared_ptr<Executor::IdleExecutors> idle =
+          std::make_shared<Executor::IdleExecutors>();
     };
+
+    std::shared_ptr<Executor> claimExecutor(Message& msg);
+    // One executor per message of a FUNCTIONS batch: execs[i] is claimed
+    // for messages[i], or null with errors[i] set if creating it failed
+    void claimExecutors(BatchExecuteRequest& req,
+                        std::vector<std::shared_ptr<Executor>>& execs,
+                        std::vector<std::string>& errors);
+    // Caller holds schedMx unique
+    std::shared_ptr<Executor> createExecutorLocked(WarmPool& pool,
+                                                   Message& msg);
+
+    // Claims take the lock SHARED (they only pop the pool's idle list,
+    // which has its own short lock); executor creation and reaping take
+    // it unique.
+    std::shared_mutex schedMx;
     std::unordered_map<std::string, std::unique_ptr<WarmPool>> executors;
     HostResources overriddenResources;
     bool resourcesOverridden = false;

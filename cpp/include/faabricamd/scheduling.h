@@ -79,6 +79,10 @@ class SchedulingDecision
                               int32_t mpiPort);
     // Returns the vacated MPI port
     int32_t removeMessage(int32_t messageId);
+    // Same, for a caller that knows the position (the planner's per-app
+    // index): O(1). A position that does not hold messageId falls back to
+    // the search above.
+    int32_t removeMessageAt(size_t pos, int32_t messageId);
     std::set<std::string> uniqueHosts() const;
     void print() const;
 };

@@ -43,12 +43,48 @@ std::vector<uint8_t> deltaApply(const std::vector<uint8_t>& oldData,
 
 void profStart(const std::string& name);
 void profEnd(const std::string& name);
+// True when FAABRIC_PROF=1; every timer below is a no-op otherwise
+bool profEnabled();
+// Steady-clock nanoseconds, for scopes that start and end on different
+// threads (profStart/profEnd pair up per thread)
+int64_t profNowNs();
+// Add one measured duration to the totals of `name`
+void profRecord(const char* name, double ms);
 std::vector<std::pair<std::string, double>> profTotalsMs();
 void profClear();
 std::string profSummary();
 
-#define PROF_START(name) ::faabricamd::profStart(#name);
-#define PROF_END(name) ::faabricamd::profEnd(#name);
+// The enabled check comes first so a disabled timer builds no std::string
+#define PROF_START(name)                                                       \
+    if (::faabricamd::profEnabled()) {                                         \
+        ::faabricamd::profStart(#name);                                        \
+    }
+#define PROF_END(name)                                                         \
+    if (::faabricamd::profEnabled()) {                                         \
+        ::faabricamd::profEnd(#name);                                          \
+    }
+
+// Scope timer for functions with several return paths
+class ProfScope
+{
+  public:
+    explicit ProfScope(const char* nameIn)
+      : name(nameIn)
+      , startNs(profEnabled() ? profNowNs() : 0)
+    {}
+    ~ProfScope()
+    {
+        if (startNs != 0) {
+            profRecord(name, (double)(profNowNs() - startNs) / 1e6);
+        }
+    }
+    ProfScope(const ProfScope&) = delete;
+    ProfScope& operator=(const ProfScope&) = delete;
+
+  private:
+    const char* name;
+    int64_t startNs;
+};
 
 // ------------------------- crash handler ------------------------------------
 // Backtrace-printing handlers for SIGABRT/SIGILL/SIGFPE; SIGSEGV stays

@@ -98,7 +98,15 @@ int32_t SchedulingDecision::removeMessage(int32_t messageId)
     if (it == messageIds.end()) {
         return 0;
     }
-    size_t idx = (size_t)std::distance(messageIds.begin(), it);
+    return removeMessageAt((size_t)std::distance(messageIds.begin(), it),
+                           messageId);
+}
+
+int32_t SchedulingDecision::removeMessageAt(size_t idx, int32_t messageId)
+{
+    if (idx >= messageIds.size() || messageIds[idx] != messageId) {
+        return removeMessage(messageId);
+    }
     int32_t port = mpiPorts[idx];
     nFunctions--;
     // Swap-and-pop: results arrive per message and vector erases shift

@@ -94,11 +94,12 @@ Executor::Executor(Message& msg)
   , boundMsg(msg)
 {
     threadPoolSize = std::min(getUsableCores(), 64);
-    threadTaskQueues.resize(threadPoolSize);
-    for (auto& q : threadTaskQueues) {
-        q = std::make_shared<Queue<ExecutorTask>>();
-    }
+    threadMailboxes.resize(threadPoolSize);
     threadPoolThreads.resize(threadPoolSize);
+    poolThreadUp = std::make_unique<std::atomic<bool>[]>(threadPoolSize);
+    for (int i = 0; i < threadPoolSize; i++) {
+        poolThreadUp[i].store(false, std::memory_order_relaxed);
+    }
     lastExecMs = getGlobalClockEpochMillis();
 }
 
@@ -173,12 +174,15 @@ void Executor::shutdown()
         if (threadPoolThreads[i].joinable()) {
             ExecutorTask stopTask;
             stopTask.stop = true;
-            threadTaskQueues[i]->enqueue(stopTask);
+            threadMailboxes[i]->post(std::move(stopTask));
         }
     }
-    for (auto& t : threadPoolThreads) {
-        if (t.joinable()) {
-            t.join();
+    for (int i = 0; i < threadPoolSize; i++) {
+        if (threadPoolThreads[i].joinable()) {
+            threadPoolThreads[i].join();
+            // A later hand-off must start a fresh thread, not post to a
+            // mailbox nobody reads
+            poolThreadUp[i].store(false, std::memory_order_release);
         }
     }
 }
@@ -201,11 +205,59 @@ void Executor::claim()
 
 void Executor::releaseClaim()
 {
+    // Unclaim first, then advertise: the other order would let a claimer
+    // pop the entry, lose the CAS and drop it, leaving this executor
+    // off the list for good
     claimed.store(false);
+    if (idleList) {
+        idleList->push(shared_from_this());
+    }
 }
 
-void Executor::executeTasks(std::vector<int> msgIdxs,
-                            std::shared_ptr<BatchExecuteRequest> req)
+void Executor::ensurePoolThreadLocked(int poolIdx)
+{
+    if (threadPoolThreads[poolIdx].joinable()) {
+        return;
+    }
+    if (!threadMailboxes[poolIdx]) {
+        threadMailboxes[poolIdx] = std::make_unique<TaskMailbox>();
+    }
+    threadPoolThreads[poolIdx] =
+      std::thread([this, poolIdx] { threadPoolThread(poolIdx); });
+    poolThreadUp[poolIdx].store(true, std::memory_order_release);
+}
+
+void Executor::postTask(int poolIdx, ExecutorTask&& task)
+{
+    task.enqueueNs = profEnabled() ? profNowNs() : 0;
+    threadMailboxes[poolIdx]->post(std::move(task));
+}
+
+void Executor::executeSingleTask(
+  int msgIdx,
+  const std::shared_ptr<BatchExecuteRequest>& req)
+{
+    if (req->type == BatchExecuteType::THREADS ||
+        !req->snapshotKey.empty() ||
+        !req->messages.at(msgIdx).snapshotKey.empty() ||
+        threadPoolSize == 0) {
+        executeTasks({ msgIdx }, req);
+        return;
+    }
+    lastExecMs = getGlobalClockEpochMillis();
+    // One task at a time on a claimed executor, so pool thread 0 is
+    // always the free one; it stays warm from batch to batch
+    if (!poolThreadUp[0].load(std::memory_order_acquire)) {
+        std::lock_guard<std::mutex> lock(threadsMx);
+        ensurePoolThreadLocked(0);
+    }
+    ExecutorTask task(msgIdx, req);
+    task.single = true;
+    postTask(0, std::move(task));
+}
+
+void Executor::executeTasks(const std::vector<int>& msgIdxs,
+                            const std::shared_ptr<BatchExecuteRequest>& req)
 {
     lastExecMs = getGlobalClockEpochMillis();
     batchCounter = std::make_shared<std::atomic<int>>((int)msgIdxs.size());
@@ -246,11 +298,8 @@ void Executor::executeTasks(std::vector<int> msgIdxs,
     std::lock_guard<std::mutex> lock(threadsMx);
     for (int msgIdx : msgIdxs) {
         int poolIdx = threadPoolSize == 0 ? 0 : msgIdx % threadPoolSize;
-        if (!threadPoolThreads[poolIdx].joinable()) {
-            threadPoolThreads[poolIdx] =
-              std::thread([this, poolIdx] { threadPoolThread(poolIdx); });
-        }
-        threadTaskQueues[poolIdx]->enqueue(ExecutorTask(msgIdx, req));
+        ensurePoolThreadLocked(poolIdx);
+        postTask(poolIdx, ExecutorTask(msgIdx, req));
     }
 }
 
@@ -490,15 +539,18 @@ void Executor::setThreadResult(Message& msg,
 void Executor::threadPoolThread(int poolIdx)
 {
     const auto& conf = getSystemConfig();
+    TaskMailbox& mailbox = *threadMailboxes[poolIdx];
     while (true) {
         ExecutorTask task;
-        try {
-            task = threadTaskQueues[poolIdx]->dequeue(conf.boundTimeout);
-        } catch (const QueueTimeoutException&) {
+        if (!mailbox.take(task, conf.boundTimeout)) {
             continue; // executor reaping handles true idleness
         }
         if (task.stop) {
             break;
+        }
+        if (task.enqueueNs != 0) {
+            profRecord("exec_wake",
+                       (double)(profNowNs() - task.enqueueNs) / 1e6);
         }
 
         Message& msg = task.req->messages.at(task.msgIdx);
@@ -533,8 +585,8 @@ void Executor::threadPoolThread(int poolIdx)
         }
         ExecutorContext::unset();
 
-        int remaining = batchCounter->fetch_sub(1) - 1;
-        bool isLastInBatch = remaining == 0;
+        bool isLastInBatch =
+          task.single || batchCounter->fetch_sub(1) - 1 == 0;
         handleTaskResult(msg, returnValue, task.req, isLastInBatch);
     }
 }

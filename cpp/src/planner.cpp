@@ -158,6 +158,7 @@ std::shared_ptr<SchedulingDecision> Planner::getPreloadedSchedulingDecision(
 std::shared_ptr<SchedulingDecision> Planner::callBatch(
   std::shared_ptr<BatchExecuteRequest> req)
 {
+    ProfScope profCallBatch("planner_call_batch");
     int32_t appId = req->appId;
     std::unique_lock lock(plannerMx);
 
@@ -442,6 +443,7 @@ void Planner::dispatchSchedulingDecision(
 {
     // Split the BER per host preserving message order
     // (reference: src/planner/Planner.cpp:1293-1390)
+    ProfScope profDispatch("planner_dispatch");
     std::map<std::string, std::shared_ptr<BatchExecuteRequest>> hostReqs;
     bool isSingleHost = decision->uniqueHosts().size() == 1;
 
@@ -551,6 +553,7 @@ void Planner::setMessageResults(
     std::vector<std::pair<std::string, int32_t>> groupClears;
     {
         std::unique_lock lock(plannerMx);
+        ProfScope profLocked("results_locked");
         for (auto& msg : msgs) {
             setMessageResultLocked(msg, waiters, batchWaiters, groupClears);
         }
@@ -617,6 +620,45 @@ void Planner::purgeOldResultsLocked()
     }
 }
 
+int64_t Planner::findInFlightPosLocked(int32_t appId,
+                                       const BatchExecuteRequest& req,
+                                       int32_t msgId)
+{
+    auto& index = state.inFlightMsgPos[appId];
+    const auto& messages = req.messages;
+    auto lookup = [&]() -> int64_t {
+        if (index.size() != messages.size()) {
+            return -2;
+        }
+        auto it = index.find(msgId);
+        if (it == index.end()) {
+            return -1;
+        }
+        if (it->second >= messages.size() ||
+            messages[it->second].id != msgId) {
+            return -2;
+        }
+        return (int64_t)it->second;
+    };
+    int64_t pos = lookup();
+    if (pos != -2) {
+        return pos;
+    }
+    // Out of step with the request (first result of the app, or the
+    // request was appended to or replaced): one linear pass. The first
+    // position wins for a repeated id, as the linear search did.
+    index.clear();
+    index.reserve(messages.size());
+    pos = -1;
+    for (size_t i = 0; i < messages.size(); i++) {
+        index.emplace(messages[i].id, (uint32_t)i);
+        if (pos < 0 && messages[i].id == msgId) {
+            pos = (int64_t)i;
+        }
+    }
+    return pos;
+}
+
 void Planner::setMessageResultLocked(
   const std::shared_ptr<Message>& msg,
   std::vector<std::pair<std::string, std::shared_ptr<Message>>>& waiters,
@@ -655,14 +697,20 @@ void Planner::setMessageResultLocked(
 
         // Release the slot exactly once per message
         auto hostIt = state.hostMap.find(msg->executedHost);
-        bool alreadySet = state.appResults[appId].count(msgId) > 0;
+        auto& appResults = state.appResults[appId];
+        auto resultIt = appResults.find(msgId);
+        bool alreadySet = resultIt != appResults.end();
         if (hostIt != state.hostMap.end() && (!alreadySet || isFrozenMsg)) {
             hostIt->second->info.usedSlots =
               std::max(0, hostIt->second->info.usedSlots - 1);
         }
 
         if (!isFrozenMsg) {
-            state.appResults[appId][msgId] = msg;
+            if (alreadySet) {
+                resultIt->second = msg;
+            } else {
+                appResults.emplace_hint(appResults.end(), msgId, msg);
+            }
         }
 
         // Remove from in-flight accounting
@@ -670,23 +718,29 @@ void Planner::setMessageResultLocked(
         if (ifIt != state.inFlightReqs.end()) {
             auto req = ifIt->second.first;
             auto decision = ifIt->second.second;
-            auto msgIt = std::find_if(
-              req->messages.begin(),
-              req->messages.end(),
-              [&](const Message& m) { return m.id == msgId; });
-            if (msgIt != req->messages.end()) {
+            int64_t pos = findInFlightPosLocked(appId, *req, msgId);
+            if (pos >= 0) {
                 // Swap-and-pop (Message is fat; a mid-vector erase moves
                 // every later message — O(n^2) per completing batch).
                 // Alignment with the decision is preserved: its
-                // removeMessage swap-and-pops the same position.
-                *msgIt = std::move(req->messages.back());
+                // removeMessageAt swap-and-pops the same position. The
+                // index follows the message that moved into the hole.
+                auto& index = state.inFlightMsgPos[appId];
+                size_t last = req->messages.size() - 1;
+                if ((size_t)pos != last) {
+                    req->messages[pos] = std::move(req->messages[last]);
+                    index[req->messages[pos].id] = (uint32_t)pos;
+                }
                 req->messages.pop_back();
-                int32_t freedPort = decision->removeMessage(msgId);
+                index.erase(msgId);
+                int32_t freedPort =
+                  decision->removeMessageAt((size_t)pos, msgId);
                 if (hostIt != state.hostMap.end()) {
                     releaseHostMpiPort(hostIt->second, freedPort);
                 }
                 if (req->messages.empty()) {
                     state.inFlightReqs.erase(appId);
+                    state.inFlightMsgPos.erase(appId);
                     state.preloadedSchedulingDecisions.erase(appId);
                     auto bwIt = state.batchDoneWaiters.find(appId);
                     if (bwIt != state.batchDoneWaiters.end()) {
@@ -770,6 +824,20 @@ size_t Planner::debugInFlightCount()
 {
     std::shared_lock lock(plannerMx);
     return state.inFlightReqs.size();
+}
+size_t Planner::debugMsgIndexCount()
+{
+    std::shared_lock lock(plannerMx);
+    return state.inFlightMsgPos.size();
+}
+int Planner::debugUsedSlots()
+{
+    std::shared_lock lock(plannerMx);
+    int used = 0;
+    for (const auto& [ip, host] : state.hostMap) {
+        used += host->info.usedSlots;
+    }
+    return used;
 }
 
 std::shared_ptr<Message> Planner::getMessageResult(const Message& msg)
@@ -917,6 +985,7 @@ void Planner::flushSchedulingState()
 {
     std::unique_lock lock(plannerMx);
     state.inFlightReqs.clear();
+    state.inFlightMsgPos.clear();
     state.appResults.clear();
     state.appResultWaiters.clear();
     state.preloadedSchedulingDecisions.clear();
@@ -1246,6 +1315,7 @@ void PlannerClient::removeHost(const Host& host)
 std::shared_ptr<SchedulingDecision> PlannerClient::callFunctions(
   std::shared_ptr<BatchExecuteRequest> req)
 {
+    ProfScope profSubmit("submit_rpc");
     std::string resp =
       rpc.syncSend((uint8_t)PlannerCalls::CallBatch, req->encode());
     auto mappings = PointToPointMappings::decode(resp);
@@ -1366,6 +1436,7 @@ std::pair<bool, int> PlannerClient::getBatchStatusCounts(int32_t appId)
 
 bool PlannerClient::waitBatchDone(int32_t appId, int timeoutMs)
 {
+    ProfScope profWait("wait_batch_done");
     // A process without a FunctionCallServer cannot receive the push —
     // registering would stall the planner's result workers on a dead
     // connection. Poll with a gentle backoff instead (matches the

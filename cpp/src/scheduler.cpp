@@ -43,84 +43,6 @@ class Scheduler::ReaperThread : public PeriodicBackgroundThread
     void doWork() override { Scheduler::get().reapStaleExecutors(); }
 };
 
-// ------------------------- dispatch helper pool ------------------------------
-// A small persistent pool that fans a batch dispatch across threads;
-// per-batch std::thread spawning measured ~0.3-0.5 ms at 128 messages.
-namespace {
-
-class DispatchPool
-{
-  public:
-    static constexpr int N = 7; // + the calling thread = 8 lanes
-
-    // Hand `fn` to every idle helper; returns how many took it
-    int run(const std::function<void()>& fn)
-    {
-        std::lock_guard<std::mutex> lock(mx);
-        ensureStarted();
-        current = fn;
-        generation++;
-        cv.notify_all();
-        return N;
-    }
-
-    // Spin-assist wait: cheap because the caller also ran `fn` and the
-    // helpers decrement within microseconds of draining
-    void awaitDone(std::atomic<int>& done, int target)
-    {
-        while (done.load(std::memory_order_acquire) < target) {
-            std::this_thread::yield();
-        }
-        std::lock_guard<std::mutex> lock(mx);
-        current = nullptr;
-    }
-
-  private:
-    void ensureStarted()
-    {
-        if (started) {
-            return;
-        }
-        started = true;
-        for (int i = 0; i < N; i++) {
-            workers.emplace_back([this] { loop(); });
-            workers.back().detach();
-        }
-    }
-
-    void loop()
-    {
-        uint64_t seen = 0;
-        while (true) {
-            std::function<void()> fn;
-            {
-                std::unique_lock<std::mutex> lock(mx);
-                cv.wait(lock, [&] {
-                    return generation != seen && current != nullptr;
-                });
-                seen = generation;
-                fn = current;
-            }
-            fn();
-        }
-    }
-
-    std::mutex mx;
-    std::condition_variable cv;
-    std::vector<std::thread> workers;
-    std::function<void()> current;
-    uint64_t generation = 0;
-    bool started = false;
-};
-
-DispatchPool& dispatchPool()
-{
-    static DispatchPool* pool = new DispatchPool(); // never destroyed
-    return *pool;
-}
-
-} // namespace
-
 Scheduler::Scheduler() = default;
 
 Scheduler& Scheduler::get()
@@ -177,23 +99,39 @@ void Scheduler::executeBatch(std::shared_ptr<BatchExecuteRequest> req)
         }
         exec->executeTasks(idxs, req);
     } else {
-        // One executor per message. The claim+enqueue is ~17 us per
-        // message (queue lock + pool-thread futex wake), so a large
-        // FUNCTIONS batch is fanned out across a few dispatcher threads
-        // instead of paying it serially (128 msgs: ~2.3 ms -> ~0.4 ms)
+        // One executor per message, all claimed in one go: the warm ones
+        // come off the pool's idle list in a single acquisition and the
+        // pool grows once for the shortfall
         size_t n = req->messages.size();
-        auto dispatchOne = [&](size_t i) {
+        std::vector<std::shared_ptr<Executor>> execs;
+        std::vector<std::string> claimErrors;
+        PROF_START(dispatch_claim)
+        claimExecutors(*req, execs, claimErrors);
+        PROF_END(dispatch_claim)
+
+        // Hand the tasks over one after the other on this thread. A
+        // hand-off is a mailbox post plus, for a sleeping pool thread, one
+        // futex wake, and that pace is what keeps the batch fast: fanning
+        // the wakes out over helper threads (as the slower queue hand-off
+        // once needed) starts every executor thread at once, they pile up
+        // on the few CPUs and on the locks every task takes, and the
+        // batch takes longer (profiles/dispatch_path_ab.json, lane sweep:
+        // 8 lanes ran at about half the rate of 1 lane at 128 messages
+        // and at a fifth at 1024)
+        PROF_START(dispatch_enqueue)
+        for (size_t i = 0; i < n; i++) {
             try {
-                PROF_START(dispatch_claim)
-                auto exec = claimExecutor(req->messages[i]);
-                PROF_END(dispatch_claim)
-                PROF_START(dispatch_enqueue)
-                exec->executeTasks({ (int)i }, req);
-                PROF_END(dispatch_enqueue)
+                if (!execs[i]) {
+                    throw FaabricException(claimErrors[i]);
+                }
+                execs[i]->executeSingleTask((int)i, req);
             } catch (const std::exception& e) {
                 // Failures set an error result instead of crashing the host
                 // (reference: src/scheduler/Scheduler.cpp:304-322)
                 FAM_ERROR("claiming executor failed: %s", e.what());
+                if (execs[i]) {
+                    execs[i]->releaseClaim();
+                }
                 auto msg = std::make_shared<Message>(req->messages[i]);
                 msg->returnValue = 1;
                 msg->executedHost = getSystemConfig().endpointHost;
@@ -201,79 +139,33 @@ void Scheduler::executeBatch(std::shared_ptr<BatchExecuteRequest> req)
                                   e.what();
                 getPlannerClient().setMessageResult(msg);
             }
-        };
-        if (n < 32) {
-            for (size_t i = 0; i < n; i++) {
-                dispatchOne(i);
-            }
-        } else {
-            // Persistent helpers (spawning 8 std::threads per batch cost
-            // ~0.3-0.5 ms); the caller thread dispatches too. Fan-outs
-            // are serialised: helpers bind to one batch at a time
-            static std::mutex fanMx;
-            std::lock_guard<std::mutex> fanLock(fanMx);
-            std::atomic<size_t> next{ 0 };
-            std::atomic<int> done{ 0 };
-            auto work = [&] {
-                size_t i;
-                while ((i = next.fetch_add(1)) < n) {
-                    dispatchOne(i);
-                }
-                done.fetch_add(1, std::memory_order_acq_rel);
-            };
-            int helpers = dispatchPool().run(work);
-            work(); // this thread participates
-            // Wait for the helpers to drain (they signal via `done`)
-            dispatchPool().awaitDone(done, helpers + 1);
         }
+        PROF_END(dispatch_enqueue)
     }
     PROF_END(sched_execute_batch)
 }
 
-std::shared_ptr<Executor> Scheduler::claimExecutor(Message& msg)
+// Caller holds schedMx (shared is enough). Pops idle-list entries until
+// one wins the claim CAS; a stale entry (claimed meanwhile, or reaped and
+// left claimed for good) is simply dropped.
+static std::shared_ptr<Executor> popIdleClaimed(
+  Executor::IdleExecutors& idle)
 {
-    std::string key = msg.user + "/" + msg.function;
-
-    // Fast path: warm reuse under the SHARED lock — tryClaim is a CAS,
-    // so concurrent dispatchers scan in parallel
-    // (reference: src/scheduler/Scheduler.cpp:339-387)
-    {
-        std::shared_lock<std::shared_mutex> rlock(schedMx);
-        auto it = executors.find(key);
-        if (it != executors.end()) {
-            auto& pool = *it->second;
-            size_t n = pool.list.size();
-            if (n > 0) {
-                // fetch_add hands every concurrent dispatcher a distinct
-                // starting slot; a shared load+store made 8 lanes chase
-                // the same executor and re-scan after CAS losses
-                size_t start =
-                  pool.hint.fetch_add(1, std::memory_order_relaxed);
-                for (size_t k = 0; k < n; k++) {
-                    size_t i = (start + k) % n;
-                    if (pool.list[i]->tryClaim()) {
-                        return pool.list[i];
-                    }
-                }
-            }
-        }
-    }
-
-    // Slow path: grow the pool under the unique lock (re-scan first —
-    // another dispatcher may have released an executor meanwhile)
-    std::unique_lock<std::shared_mutex> lock(schedMx);
-    auto& poolPtr = executors[key];
-    if (!poolPtr) {
-        poolPtr = std::make_unique<WarmPool>();
-    }
-    auto& pool = *poolPtr;
-    for (auto& e : pool.list) {
+    std::shared_ptr<Executor> e;
+    while (idle.pop(e)) {
         if (e->tryClaim()) {
             return e;
         }
     }
+    return nullptr;
+}
+
+std::shared_ptr<Executor> Scheduler::createExecutorLocked(WarmPool& pool,
+                                                          Message& msg)
+{
     auto exec = getExecutorFactory()->createExecutor(msg);
     exec->claim();
+    exec->setIdleList(pool.idle);
     if (getNumGpus() > 0) {
         const auto& conf = getSystemConfig();
         // A worker pinned to one GPU (FAABRIC_GPU_DEVICE) keeps every
@@ -287,6 +179,110 @@ std::shared_ptr<Executor> Scheduler::claimExecutor(Message& msg)
     return exec;
 }
 
+std::shared_ptr<Executor> Scheduler::claimExecutor(Message& msg)
+{
+    std::string key = msg.user + "/" + msg.function;
+
+    // Fast path: warm reuse under the SHARED lock, O(1) off the idle list
+    // (reference: src/scheduler/Scheduler.cpp:339-387)
+    {
+        std::shared_lock<std::shared_mutex> rlock(schedMx);
+        auto it = executors.find(key);
+        if (it != executors.end()) {
+            if (auto e = popIdleClaimed(*it->second->idle)) {
+                return e;
+            }
+        }
+    }
+
+    // Slow path: grow the pool under the unique lock (re-check first —
+    // an executor may have been released meanwhile)
+    std::unique_lock<std::shared_mutex> lock(schedMx);
+    auto& poolPtr = executors[key];
+    if (!poolPtr) {
+        poolPtr = std::make_unique<WarmPool>();
+    }
+    if (auto e = popIdleClaimed(*poolPtr->idle)) {
+        return e;
+    }
+    return createExecutorLocked(*poolPtr, msg);
+}
+
+void Scheduler::claimExecutors(
+  BatchExecuteRequest& req,
+  std::vector<std::shared_ptr<Executor>>& execs,
+  std::vector<std::string>& errors)
+{
+    size_t n = req.messages.size();
+    execs.assign(n, nullptr);
+    errors.assign(n, std::string());
+
+    // Pools are per function: a batch that mixes functions (not what the
+    // batch factory builds) claims message by message
+    const Message& first = req.messages[0];
+    bool oneFunction = true;
+    for (size_t i = 1; i < n && oneFunction; i++) {
+        oneFunction = req.messages[i].function == first.function &&
+                      req.messages[i].user == first.user;
+    }
+    if (!oneFunction) {
+        for (size_t i = 0; i < n; i++) {
+            try {
+                execs[i] = claimExecutor(req.messages[i]);
+            } catch (const std::exception& e) {
+                errors[i] = e.what();
+            }
+        }
+        return;
+    }
+
+    std::string key = first.user + "/" + first.function;
+    std::vector<std::shared_ptr<Executor>> popped;
+    popped.reserve(n);
+    size_t got = 0;
+    // Take up to (n - got) idle entries in one acquisition, keep those
+    // that win the claim CAS; repeat only if stale entries were dropped
+    auto takeIdle = [&](Executor::IdleExecutors& idle) {
+        while (got < n) {
+            popped.clear();
+            if (idle.popMany(n - got, popped) == 0) {
+                return;
+            }
+            for (auto& e : popped) {
+                if (e->tryClaim()) {
+                    execs[got++] = std::move(e);
+                }
+            }
+        }
+    };
+    {
+        std::shared_lock<std::shared_mutex> rlock(schedMx);
+        auto it = executors.find(key);
+        if (it != executors.end()) {
+            takeIdle(*it->second->idle);
+        }
+    }
+    if (got == n) {
+        return;
+    }
+
+    // Shortfall: grow the pool once, under one unique acquisition
+    std::unique_lock<std::shared_mutex> lock(schedMx);
+    auto& poolPtr = executors[key];
+    if (!poolPtr) {
+        poolPtr = std::make_unique<WarmPool>();
+    }
+    takeIdle(*poolPtr->idle);
+    poolPtr->list.reserve(poolPtr->list.size() + (n - got));
+    for (; got < n; got++) {
+        try {
+            execs[got] = createExecutorLocked(*poolPtr, req.messages[got]);
+        } catch (const std::exception& e) {
+            errors[got] = e.what();
+        }
+    }
+}
+
 int Scheduler::reapStaleExecutors()
 {
     std::unique_lock<std::shared_mutex> lock(schedMx);
@@ -296,8 +292,12 @@ int Scheduler::reapStaleExecutors()
         auto& list = pool->list;
         for (auto it = list.begin(); it != list.end();) {
             auto& exec = *it;
-            if (!exec->isClaimed() &&
-                exec->getMillisSinceLastExec() > conf.boundTimeout) {
+            // Reaping takes the claim and never gives it back: an idle-list
+            // entry pushed by a release that raced with this check then
+            // loses its CAS and is dropped by whoever pops it
+            if (exec->getMillisSinceLastExec() > conf.boundTimeout &&
+                exec->tryClaim()) {
+                pool->idle->remove(exec);
                 exec->shutdown();
                 it = list.erase(it);
                 reaped++;
@@ -397,6 +397,7 @@ void Scheduler::flushLocally()
 {
     std::unique_lock<std::shared_mutex> lock(schedMx);
     for (auto& [key, pool] : executors) {
+        pool->idle->close();
         for (auto& e : pool->list) {
             e->flush();
         }
@@ -410,6 +411,7 @@ void Scheduler::shutdown()
     stopReaper();
     std::unique_lock<std::shared_mutex> lock(schedMx);
     for (auto& [key, pool] : executors) {
+        pool->idle->close();
         for (auto& e : pool->list) {
             e->shutdown();
         }
@@ -443,6 +445,16 @@ size_t Scheduler::getExecutorCount()
     size_t n = 0;
     for (auto& [key, pool] : executors) {
         n += pool->list.size();
+    }
+    return n;
+}
+
+size_t Scheduler::debugIdleCount()
+{
+    std::shared_lock<std::shared_mutex> lock(schedMx);
+    size_t n = 0;
+    for (auto& [key, pool] : executors) {
+        n += pool->idle->size();
     }
     return n;
 }
@@ -511,8 +523,10 @@ void FunctionCallServer::doAsyncRecv(uint8_t code,
     (void)seq;
     switch ((FunctionCalls)code) {
         case FunctionCalls::ExecuteFunctions: {
+            PROF_START(exec_decode)
             auto req = std::make_shared<BatchExecuteRequest>(
               BatchExecuteRequest::decode(body));
+            PROF_END(exec_decode)
             Scheduler::get().executeBatch(req);
             break;
         }

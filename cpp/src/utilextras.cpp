@@ -272,10 +272,28 @@ thread_local std::map<std::string, std::chrono::steady_clock::time_point>
 // PROF macros behind TRACE_ALL for the same reason: map + mutex work on
 // every call is measurable in hot paths (3 pairs per message in the
 // batch path)
-static bool profEnabled()
+bool profEnabled()
 {
     static const bool v = getEnvVarInt("FAABRIC_PROF", 0) != 0;
     return v;
+}
+
+int64_t profNowNs()
+{
+    return std::chrono::duration_cast<std::chrono::nanoseconds>(
+             std::chrono::steady_clock::now().time_since_epoch())
+      .count();
+}
+
+void profRecord(const char* name, double ms)
+{
+    if (!profEnabled()) {
+        return;
+    }
+    auto& st = profState();
+    std::lock_guard<std::mutex> lock(st.mx);
+    st.totalsMs[name] += ms;
+    st.counts[name] += 1;
 }
 
 void profStart(const std::string& name)
