@@ -319,6 +319,32 @@ void initOpsBindings(py::module_& m)
                   throw FaabricException("famFillRandom failed");
               }
           });
+    // Thin wrappers over the D2D copy and whole-buffer XOR kernels (null
+    // stream, synchronised) so they can be driven without an MPI world
+    m.def("fam_copy_buffer",
+          [](uintptr_t src, uintptr_t dst, uint64_t bytes) {
+              py::gil_scoped_release release;
+              hipError_t rc = famCopyBuffer(
+                (const void*)src, (void*)dst, bytes, nullptr);
+              if (rc == hipSuccess) {
+                  rc = hipDeviceSynchronize();
+              }
+              if (rc != hipSuccess) {
+                  throw FaabricException("famCopyBuffer failed");
+              }
+          });
+    m.def("fam_xor_buffer",
+          [](uintptr_t a, uintptr_t b, uintptr_t out, uint64_t bytes) {
+              py::gil_scoped_release release;
+              hipError_t rc = famXorBuffer(
+                (const void*)a, (const void*)b, (void*)out, bytes, nullptr);
+              if (rc == hipSuccess) {
+                  rc = hipDeviceSynchronize();
+              }
+              if (rc != hipSuccess) {
+                  throw FaabricException("famXorBuffer failed");
+              }
+          });
     m.def("fam_touch_pages",
           [](uintptr_t ptr, const std::vector<uint32_t>& pages,
              uint64_t seed) {

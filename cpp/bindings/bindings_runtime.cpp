@@ -7,6 +7,7 @@
 #include "faabricamd/executor.h"
 #include "faabricamd/flat.h"
 #include "faabricamd/hipipc.h"
+#include "faabricamd/mpi.h"
 #include "faabricamd/planner.h"
 #include "faabricamd/ptp.h"
 #include "faabricamd/runner.h"
@@ -958,6 +959,32 @@ void initRuntimeBindings(py::module_& m)
           },
           py::arg("n_pages"),
           py::arg("set_bits"));
+    // The host plane's op_reduce combine on two equal-length byte strings
+    // holding `dtype` elements: returns inout after inout = op(inout, in)
+    m.def("_debug_op_reduce_host",
+          [](int op, int dtype, const py::bytes& inBytes,
+             const py::bytes& inoutBytes) {
+              if (op < 0 || op > (int)MpiOp::PROD || dtype < 0 ||
+                  dtype > (int)MpiDataType::BYTE) {
+                  throw FaabricException("bad op or dtype");
+              }
+              std::string in = inBytes;
+              std::string inout = inoutBytes;
+              size_t elem = mpiTypeSize((MpiDataType)dtype);
+              if (in.size() != inout.size() || (in.size() % elem) != 0) {
+                  throw FaabricException("operand length mismatch");
+              }
+              MpiWorld::opReduceHost((MpiOp)op,
+                                     (MpiDataType)dtype,
+                                     (int)(inout.size() / elem),
+                                     (const uint8_t*)in.data(),
+                                     (uint8_t*)inout.data());
+              return py::bytes(inout.data(), inout.size());
+          },
+          py::arg("op"),
+          py::arg("dtype"),
+          py::arg("in_bytes"),
+          py::arg("inout_bytes"));
     m.def("wait_batch_done",
           [](int32_t appId, int timeoutMs) {
               py::gil_scoped_release release;

@@ -328,10 +328,12 @@ __device__ __forceinline__ T famApply(int op, T a, T b)
     switch (op) {
         case FAM_OP_SUM:
             return a + b;
+        // Operand order of std::max/std::min(inout, in), as the host plane
+        // (opReduceLoop): a NaN operand or a +0.0/-0.0 tie keeps `a`
         case FAM_OP_MAX:
-            return a > b ? a : b;
+            return a < b ? b : a;
         case FAM_OP_MIN:
-            return a < b ? a : b;
+            return b < a ? b : a;
         case FAM_OP_PROD:
             return a * b;
         case FAM_OP_SUB:
@@ -548,8 +550,10 @@ hipError_t famCopyBuffer(const void* src,
                          uint64_t bytes,
                          hipStream_t stream)
 {
-    if ((bytes % 16) != 0) {
-        // Tail not vectorisable: fall back to the runtime copy
+    if ((bytes % 16) != 0 ||
+        (((uintptr_t)src | (uintptr_t)dst) & 15) != 0) {
+        // Tail or base not vectorisable (callers pass user pointers, e.g.
+        // a tensor view at a 4 B offset): fall back to the runtime copy
         return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice,
                               stream);
     }
@@ -787,6 +791,12 @@ hipError_t famElementwiseOp(void* inout,
                             int op,
                             hipStream_t stream)
 {
+    // An unknown dtype or op, or XOR on a typed dtype, has no kernel: an
+    // error, never a launch that writes every element back unchanged
+    if (dtype < 0 || dtype > 5 || op < FAM_OP_SUM || op > FAM_OP_XOR ||
+        (op == FAM_OP_XOR && dtype != 5)) {
+        return hipErrorInvalidValue;
+    }
     dim3 grid(gridFor(count));
     dim3 block(FAM_KERNEL_BLOCK);
     switch (dtype) {

@@ -325,11 +325,13 @@ class MpiWorld
                                  size_t bytes,
                                  MpiMessageType type);
 
-    void opReduceHost(MpiOp op,
-                      MpiDataType type,
-                      int count,
-                      const uint8_t* in,
-                      uint8_t* inout);
+  public:
+    // Host-plane combine inout[i] = op(inout[i], in[i]); stateless
+    static void opReduceHost(MpiOp op,
+                             MpiDataType type,
+                             int count,
+                             const uint8_t* in,
+                             uint8_t* inout);
 };
 
 class MpiWorldRegistry
