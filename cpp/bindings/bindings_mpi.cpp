@@ -192,7 +192,8 @@ void initMpiBindings(py::module_& m)
                                   (const uint8_t*)s.data(),
                                   out.data(),
                                   MpiDataType::BYTE,
-                                  chunkBytes);
+                                  chunkBytes,
+                                  MpiBufferLoc::HOST);
               }
               return py::bytes((const char*)out.data(), out.size());
           });
@@ -211,7 +212,8 @@ void initMpiBindings(py::module_& m)
                                  (const uint8_t*)s.data(),
                                  out.data(),
                                  MpiDataType::BYTE,
-                                 (int)s.size());
+                                 (int)s.size(),
+                                 MpiBufferLoc::HOST);
               }
               return py::bytes((const char*)out.data(), out.size());
           });
@@ -412,6 +414,59 @@ void initMpiBindings(py::module_& m)
                                dtype,
                                countPerRank,
                                MpiBufferLoc::AUTO);
+          });
+    m.def("mpi_scatter_ptr",
+          [](int root,
+             int rank,
+             uintptr_t sendPtr,
+             uintptr_t recvPtr,
+             int countPerRank,
+             MpiDataType dtype) {
+              py::gil_scoped_release release;
+              world().scatter(root,
+                              rank,
+                              (const uint8_t*)sendPtr,
+                              (uint8_t*)recvPtr,
+                              dtype,
+                              countPerRank,
+                              MpiBufferLoc::AUTO);
+          });
+    m.def("mpi_gather_ptr",
+          [](int rank,
+             int root,
+             uintptr_t sendPtr,
+             uintptr_t recvPtr,
+             int countPerRank,
+             MpiDataType dtype) {
+              py::gil_scoped_release release;
+              world().gather(rank,
+                             root,
+                             (const uint8_t*)sendPtr,
+                             (uint8_t*)recvPtr,
+                             dtype,
+                             countPerRank,
+                             MpiBufferLoc::AUTO);
+          });
+    // Each buffer's location is probed on its own; a host/device pair
+    // works on the PTP device plane and throws on the RCCL plane
+    m.def("mpi_sendrecv_ptr",
+          [](int rank,
+             int sendTo,
+             int recvFrom,
+             uintptr_t sendPtr,
+             uintptr_t recvPtr,
+             int count,
+             MpiDataType dtype) {
+              py::gil_scoped_release release;
+              world().sendRecv((const uint8_t*)sendPtr,
+                               count,
+                               dtype,
+                               sendTo,
+                               (uint8_t*)recvPtr,
+                               count,
+                               dtype,
+                               recvFrom,
+                               rank);
           });
     m.def("mpi_send_ptr",
           [](int sendRank,

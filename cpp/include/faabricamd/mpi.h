@@ -184,13 +184,15 @@ class MpiWorld
                  const uint8_t* sendBuffer,
                  uint8_t* recvBuffer,
                  MpiDataType dataType,
-                 int count);
+                 int count,
+                 MpiBufferLoc loc = MpiBufferLoc::AUTO);
     void gather(int thisRank,
                 int rootRank,
                 const uint8_t* sendBuffer,
                 uint8_t* recvBuffer,
                 MpiDataType dataType,
-                int count);
+                int count,
+                MpiBufferLoc loc = MpiBufferLoc::AUTO);
     void allGather(int thisRank,
                    const uint8_t* sendBuffer,
                    uint8_t* recvBuffer,

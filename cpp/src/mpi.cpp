@@ -663,6 +663,9 @@ void MpiWorld::deviceReduceFallback(int thisRank,
                                     MpiOp op)
 {
     size_t bytes = mpiTypeSize(dataType) * (size_t)count;
+    if (bytes == 0) {
+        return; // the count is the same on every rank: nothing to fold
+    }
     if (thisRank != rootRank) {
         devSend(thisRank, rootRank, sendBuffer, bytes,
                 MpiMessageType::REDUCE);
@@ -761,11 +764,9 @@ void MpiWorld::recv(int sendRank,
                     MpiBufferLoc loc)
 {
     size_t bytes = mpiTypeSize(dataType) * (size_t)count;
-    if (isDeviceBuffer(buffer, loc)) {
-        if (!rcclUsable(recvRank)) {
-            devRecv(sendRank, recvRank, buffer, bytes, messageType);
-            return;
-        }
+    bool onDevice = isDeviceBuffer(buffer, loc);
+    if (onDevice && rcclUsable(recvRank)) {
+        // The rank stream orders this receive after any earlier irecv
         ncclComm_t comm;
         hipStream_t stream;
         {
@@ -781,8 +782,8 @@ void MpiWorld::recv(int sendRank,
     }
 
     // Pending irecvs on this channel must drain first to preserve MPI
-    // matching order (reference: recvBatchReturnLast
-    // src/mpi/MpiWorld.cpp:1963-2030)
+    // matching order, on the host plane and the PTP device plane alike
+    // (reference: recvBatchReturnLast src/mpi/MpiWorld.cpp:1963-2030)
     for (auto& p : rankState.pendingRecvs) {
         if (!p.done && p.sendRank == sendRank && p.recvRank == recvRank &&
             p.type == messageType) {
@@ -796,6 +797,10 @@ void MpiWorld::recv(int sendRank,
             }
             p.done = true;
         }
+    }
+    if (onDevice) {
+        devRecv(sendRank, recvRank, buffer, bytes, messageType);
+        return;
     }
     auto data = hostRecv(sendRank, recvRank, bytes, messageType);
     std::memcpy(buffer, data.data(), data.size());
@@ -941,7 +946,39 @@ void MpiWorld::sendRecv(const uint8_t* sendBuffer,
                         int recvFromRank,
                         int thisRank)
 {
-    if (isDeviceBuffer(sendBuffer, MpiBufferLoc::AUTO)) {
+    // Each buffer is probed on its own: a host pointer never reaches the
+    // device plane and a device pointer never reaches a host memcpy
+    bool sendOnDevice = isDeviceBuffer(sendBuffer, MpiBufferLoc::AUTO);
+    bool recvOnDevice = isDeviceBuffer(recvBuffer, MpiBufferLoc::AUTO);
+    if (sendOnDevice != recvOnDevice) {
+        if (rcclUsable(thisRank)) {
+            throw FaabricException(
+              "sendRecv with one host and one device buffer is only "
+              "supported on the PTP device plane");
+        }
+        // The PTP broker converts between host and device payloads, so
+        // each side rides its own plane. Sends are buffered on both, so
+        // send-then-recv cannot deadlock in a ring.
+        size_t sendBytes = mpiTypeSize(sendType) * (size_t)sendCount;
+        size_t recvBytes = mpiTypeSize(recvType) * (size_t)recvCount;
+        if (sendOnDevice) {
+            devSend(thisRank, sendToRank, sendBuffer, sendBytes,
+                    MpiMessageType::SENDRECV);
+        } else {
+            hostSend(thisRank, sendToRank, sendBuffer, sendBytes,
+                     MpiMessageType::SENDRECV);
+        }
+        if (recvOnDevice) {
+            devRecv(recvFromRank, thisRank, recvBuffer, recvBytes,
+                    MpiMessageType::SENDRECV);
+        } else {
+            auto data = hostRecv(recvFromRank, thisRank, recvBytes,
+                                 MpiMessageType::SENDRECV);
+            std::memcpy(recvBuffer, data.data(), data.size());
+        }
+        return;
+    }
+    if (sendOnDevice) {
         if (!rcclUsable(thisRank)) {
             // Buffered device sends never rendezvous, so send-then-recv
             // cannot deadlock in a ring
@@ -1146,9 +1183,32 @@ void MpiWorld::scatter(int rootRank,
                        const uint8_t* sendBuffer,
                        uint8_t* recvBuffer,
                        MpiDataType dataType,
-                       int count)
+                       int count,
+                       MpiBufferLoc loc)
 {
     size_t bytes = mpiTypeSize(dataType) * (size_t)count;
+    // Only the root's sendBuffer is significant, so every rank probes the
+    // buffer it always has
+    if (isDeviceBuffer(recvBuffer, loc)) {
+        // PTP device plane on every deployment (it works with or without
+        // RCCL): remote chunks leave straight from sendBuffer + i*bytes
+        if (thisRank != rootRank) {
+            devRecv(rootRank, thisRank, recvBuffer, bytes,
+                    MpiMessageType::SCATTER);
+            return;
+        }
+        for (int i = 0; i < size; i++) {
+            const uint8_t* chunk = sendBuffer + (size_t)i * bytes;
+            if (i != rootRank) {
+                devSend(rootRank, i, chunk, bytes, MpiMessageType::SCATTER);
+            } else if (recvBuffer != chunk && bytes > 0) {
+                hipStream_t s = (hipStream_t)fallbackStream();
+                HIP_CHECK(famCopyBuffer(chunk, recvBuffer, bytes, s));
+                HIP_CHECK(hipStreamSynchronize(s));
+            }
+        }
+        return;
+    }
     if (thisRank == rootRank) {
         for (int i = 0; i < size; i++) {
             const uint8_t* chunk = sendBuffer + (size_t)i * bytes;
@@ -1173,12 +1233,37 @@ void MpiWorld::gather(int thisRank,
                       const uint8_t* sendBuffer,
                       uint8_t* recvBuffer,
                       MpiDataType dataType,
-                      int count)
+                      int count,
+                      MpiBufferLoc loc)
 {
+    size_t bytes = mpiTypeSize(dataType) * (size_t)count;
+    // Only the root's recvBuffer is significant, so every rank probes the
+    // buffer it always has
+    if (isDeviceBuffer(sendBuffer, loc)) {
+        // PTP device plane on every deployment (it works with or without
+        // RCCL): remote chunks land straight in recvBuffer + i*bytes
+        if (thisRank != rootRank) {
+            devSend(thisRank, rootRank, sendBuffer, bytes,
+                    MpiMessageType::GATHER);
+            return;
+        }
+        uint8_t* own = recvBuffer + (size_t)rootRank * bytes;
+        if (own != sendBuffer && bytes > 0) {
+            hipStream_t s = (hipStream_t)fallbackStream();
+            HIP_CHECK(famCopyBuffer(sendBuffer, own, bytes, s));
+            HIP_CHECK(hipStreamSynchronize(s));
+        }
+        for (int i = 0; i < size; i++) {
+            if (i != rootRank) {
+                devRecv(i, rootRank, recvBuffer + (size_t)i * bytes, bytes,
+                        MpiMessageType::GATHER);
+            }
+        }
+        return;
+    }
     // Two-level host plane: leaders gather their host's chunks in rank
     // order and send one batched buffer to the root, which unpacks by
     // the shared ranksPerHost layout (reference: :917-1080)
-    size_t bytes = mpiTypeSize(dataType) * (size_t)count;
     auto hostsMap = ranksPerHost();
     const std::string& rootHost = getHostForRank(rootRank);
     const std::string& myHost = getHostForRank(thisRank);
@@ -1290,7 +1375,8 @@ void MpiWorld::allGather(int thisRank,
         return;
     }
     // gather at 0, then broadcast the full buffer (reference: :1082-1111)
-    gather(thisRank, 0, sendBuffer, recvBuffer, dataType, count);
+    gather(thisRank, 0, sendBuffer, recvBuffer, dataType, count,
+           MpiBufferLoc::HOST);
     broadcast(0,
               thisRank,
               recvBuffer,
@@ -1560,6 +1646,9 @@ void MpiWorld::scan(int thisRank,
         if (!rcclUsable(thisRank)) {
             // Linear chain over the PTP device plane with the same
             // fused elementwise combine
+            if (bytes == 0) {
+                return; // same count on every rank: no chain to run
+            }
             hipStream_t s = (hipStream_t)fallbackStream();
             if (recvBuffer != sendBuffer) {
                 HIP_CHECK(famCopyBuffer(sendBuffer, recvBuffer, bytes,
@@ -1639,6 +1728,9 @@ void MpiWorld::reduceScatter(int thisRank,
             // slice over the device plane
             size_t sliceBytes = mpiTypeSize(dataType) * (size_t)recvCount;
             size_t fullBytes = sliceBytes * (size_t)size;
+            if (sliceBytes == 0) {
+                return; // same count on every rank: no slice to send
+            }
             hipStream_t s = (hipStream_t)fallbackStream();
             if (thisRank == 0) {
                 uint8_t* full = nullptr;

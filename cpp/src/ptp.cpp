@@ -605,6 +605,14 @@ void PointToPointBroker::sendMessageDevice(int32_t appId,
                                            size_t size,
                                            bool mustOrderMsgs)
 {
+    if (size == 0) {
+        // Nothing to stage: an empty message keeps the channel's order
+        // without a zero-byte device allocation or arena segment (an
+        // empty segment would take the offset of one still in flight)
+        sendMessage(appId, groupId, sendIdx, recvIdx, nullptr, 0,
+                    mustOrderMsgs);
+        return;
+    }
     uint32_t seq = NO_SEQ;
     if (mustOrderMsgs) {
         std::lock_guard<std::mutex> lock(sendSeqMx);
@@ -729,6 +737,9 @@ size_t PointToPointBroker::recvMessageDevice(int32_t groupId,
     }
     if (p.host.size() > capacity) {
         throw FaabricException("ptp device recv buffer too small");
+    }
+    if (p.host.empty()) {
+        return 0;
     }
     if (hipMemcpyAsync(devPtr, p.host.data(), p.host.size(),
                        hipMemcpyHostToDevice, s) != hipSuccess ||
