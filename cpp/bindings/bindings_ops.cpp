@@ -4,6 +4,7 @@
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
+#include "faabricamd/executor.h"
 #include "faabricamd/ops.h"
 #include "faabricamd/util.h"
 
@@ -262,8 +263,71 @@ void initOpsBindings(py::module_& m)
       .def("apply_last_diff", [](DeviceSnapshot& s) {
           py::gil_scoped_release release;
           s.applyLastDiff();
+      })
+      // Typed merge regions: the packed TypedElems diff of one region
+      // (None when no element changed), its merge, the full thread diff
+      // under a region list of (offset, length, data_type, operation)
+      // tuples, and the join-time queue
+      .def("typed_diff",
+           [](DeviceSnapshot& s,
+              uintptr_t ptr,
+              uint32_t offset,
+              size_t length,
+              SnapshotDataType dataType,
+              SnapshotMergeOperation operation) {
+               py::gil_scoped_release release;
+               return s.typedDiff(
+                 (const void*)ptr,
+                 SnapshotMergeRegion(offset, length, dataType, operation));
+           },
+           py::arg("ptr"),
+           py::arg("offset"),
+           py::arg("length"),
+           py::arg("data_type"),
+           py::arg("operation"))
+      .def("apply_typed_diff",
+           [](DeviceSnapshot& s, const SnapshotDiff& diff) {
+               py::gil_scoped_release release;
+               s.applyTypedDiff(diff);
+           })
+      .def("diff_with_regions",
+           [](DeviceSnapshot& s,
+              uintptr_t ptr,
+              const std::vector<std::tuple<uint32_t, size_t, int, int>>&
+                regions) {
+               std::vector<SnapshotMergeRegion> mr;
+               for (const auto& [off, len, dt, op] : regions) {
+                   mr.emplace_back(off,
+                                   len,
+                                   (SnapshotDataType)dt,
+                                   (SnapshotMergeOperation)op);
+               }
+               py::gil_scoped_release release;
+               return s.diffWithRegions((const void*)ptr, mr);
+           },
+           py::arg("ptr"),
+           py::arg("regions"))
+      .def("queue_diff",
+           [](DeviceSnapshot& s, const SnapshotDiff& diff) {
+               s.queueDiff(diff);
+           })
+      .def("apply_queued_diffs", [](DeviceSnapshot& s) {
+          py::gil_scoped_release release;
+          return s.applyQueuedPackedDiffs();
       });
 
+    // The device merge regions registered on this host under the running
+    // task's snapshot key, as (offset, length, data_type, operation)
+    m.def("executor_device_merge_regions", [] {
+        const Message& msg = ExecutorContext::get().getMsg();
+        std::vector<std::tuple<uint32_t, size_t, int, int>> out;
+        for (const auto& r :
+             DeviceSnapshotRegistry::get().getMergeRegions(msg.snapshotKey)) {
+            out.emplace_back(
+              r.offset, r.length, (int)r.dataType, (int)r.operation);
+        }
+        return out;
+    });
     m.def("device_elementwise_op",
           [](uintptr_t inout,
              uintptr_t in,

@@ -620,7 +620,9 @@ void initRuntimeBindings(py::module_& m)
       .value("Subtract", SnapshotMergeOperation::Subtract)
       .value("Max", SnapshotMergeOperation::Max)
       .value("Min", SnapshotMergeOperation::Min)
-      .value("XOR", SnapshotMergeOperation::XOR);
+      .value("XOR", SnapshotMergeOperation::XOR)
+      .value("XorPages", SnapshotMergeOperation::XorPages)
+      .value("TypedElems", SnapshotMergeOperation::TypedElems);
 
     py::class_<SnapshotDiff>(m, "SnapshotDiff")
       .def(py::init<>())

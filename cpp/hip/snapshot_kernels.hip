@@ -458,6 +458,271 @@ __global__ __launch_bounds__(FAM_KERNEL_BLOCK) void famKvCommitPagesKernel(
     }
 }
 
+// ---------------------------------------------------------------------------
+// Typed merge regions (THREADS fork-join over a shared reduction variable):
+//
+//  typedDiffKernel<T> — one WAVE per 4 KiB-aligned chunk of the region.
+//      An element is changed when !(orig == cur) as T (calcDiffValue in
+//      cpp/src/snapshot.cpp: NaN always, +0.0 vs -0.0 never). The wave
+//      counts its changed elements per lane, scans the counts as
+//      compactPageIdxKernel does and takes ONE ticket per chunk (none when
+//      nothing changed), then every lane writes its own run of
+//      {element index, value} entries. The 16 B-aligned interior of the
+//      chunk loads 16 B per lane (4 vectors per lane, as the page diff);
+//      the region's head and tail elements up to the next 16 B boundary
+//      take a scalar load in the low lanes.
+//  applyTypedElemsKernel<T> — base[idx[i]] = op(base[idx[i]], val[i]), one
+//      lane per entry, cached RMW. Diffs are applied one after another on
+//      one stream and an index occurs once per diff: no atomics.
+//
+// op is a SnapshotMergeOperation code, dtype a SnapshotDataType code.
+// ---------------------------------------------------------------------------
+enum FamMergeOp : int
+{
+    FAM_MERGE_SUM = 1,
+    FAM_MERGE_PRODUCT = 2,
+    FAM_MERGE_SUBTRACT = 3,
+    FAM_MERGE_MAX = 4,
+    FAM_MERGE_MIN = 5,
+};
+
+template<typename T>
+struct TypedUnsigned
+{
+    using type = T; // floats subtract as themselves
+};
+template<>
+struct TypedUnsigned<int32_t>
+{
+    using type = u32;
+};
+template<>
+struct TypedUnsigned<int64_t>
+{
+    using type = u64;
+};
+
+// 0 = unchanged, 1 = emit `out`, 2 = product diff with a zero original
+template<typename T>
+__device__ __forceinline__ int typedDiffValue(int op, T orig, T cur, T& out)
+{
+    using U = typename TypedUnsigned<T>::type;
+    if (orig == cur) {
+        return 0;
+    }
+    switch (op) {
+        case FAM_MERGE_SUM:
+            // Integers wrap (two's complement): subtract unsigned
+            out = (T)((U)cur - (U)orig);
+            return 1;
+        case FAM_MERGE_SUBTRACT:
+            out = (T)((U)orig - (U)cur);
+            return 1;
+        case FAM_MERGE_PRODUCT:
+            if (orig == (T)0) {
+                return 2;
+            }
+            out = cur / orig;
+            return 1;
+        default: // Max, Min ship the value
+            out = cur;
+            return 1;
+    }
+}
+
+template<typename T>
+__global__ __launch_bounds__(FAM_KERNEL_BLOCK) void typedDiffKernel(
+  const u8* __restrict__ snap,
+  const u8* __restrict__ cur,
+  u64 regionStart, // bytes, multiple of sizeof(T)
+  u64 regionEnd,   // bytes, regionStart + nElems * sizeof(T)
+  int op,
+  u32* __restrict__ ticket,
+  u32* __restrict__ errWord,
+  u32* __restrict__ idxOut,
+  T* __restrict__ valOut)
+{
+    constexpr u32 E = 16 / sizeof(T); // elements per 16 B vector
+    const u32 lane = threadIdx.x & 63;
+    const u64 waveId = ((u64)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+
+    // This wave's chunk, clipped to the region (all wave-uniform)
+    const u64 chunk = regionStart / FAM_PAGE + waveId;
+    u64 lo = chunk * FAM_PAGE;
+    u64 hi = lo + FAM_PAGE;
+    lo = lo < regionStart ? regionStart : lo;
+    hi = hi > regionEnd ? regionEnd : hi;
+    if (lo >= hi) {
+        return;
+    }
+    // Elements never straddle a 16 B boundary: regionStart is a multiple
+    // of sizeof(T), which divides 16
+    u64 alo = (lo + 15) & ~(u64)15;
+    u64 ahi = hi & ~(u64)15;
+    if (alo > hi) {
+        alo = hi; // the whole clip lies inside one 16 B line
+    }
+    if (ahi < alo) {
+        ahi = alo;
+    }
+    const u32 nHead = (u32)((alo - lo) / sizeof(T)); // < E
+    const u32 nTail = (u32)((hi - ahi) / sizeof(T)); // < E
+    const u32 nVec = (u32)((ahi - alo) / 16);        // <= 256
+
+    // Interior: 4 vectors per lane, loads issued before any compare
+    uint4 s[4];
+    uint4 c[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        u32 v = lane + 64 * k;
+        if (v < nVec) {
+            s[k] = ldVec<true>((const uint4*)(snap + alo) + v);
+            c[k] = ldVec<true>((const uint4*)(cur + alo) + v);
+        } else {
+            s[k] = make_uint4(0, 0, 0, 0);
+            c[k] = s[k];
+        }
+    }
+    // Head and tail: one scalar element in each of the low lanes
+    T hs = (T)0, hc = (T)0, ts = (T)0, tc = (T)0;
+    if (lane < nHead) {
+        hs = *(const T*)(snap + lo + lane * sizeof(T));
+        hc = *(const T*)(cur + lo + lane * sizeof(T));
+    }
+    if (lane < nTail) {
+        ts = *(const T*)(snap + ahi + lane * sizeof(T));
+        tc = *(const T*)(cur + ahi + lane * sizeof(T));
+    }
+
+    // Pass 1: which of this lane's elements emit an entry
+    u32 emitMask = 0; // bit k*E+e interior, bit 16 head, bit 17 tail
+    bool zeroOrig = false;
+    T tmp = (T)0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        T sv[E];
+        T cv[E];
+        __builtin_memcpy(sv, &s[k], 16);
+        __builtin_memcpy(cv, &c[k], 16);
+#pragma unroll
+        for (u32 e = 0; e < E; e++) {
+            int r = typedDiffValue<T>(op, sv[e], cv[e], tmp);
+            emitMask |= (r == 1 ? 1u : 0u) << (k * E + e);
+            zeroOrig |= r == 2;
+        }
+    }
+    {
+        int r = typedDiffValue<T>(op, hs, hc, tmp);
+        emitMask |= (r == 1 ? 1u : 0u) << 16;
+        zeroOrig |= r == 2;
+        r = typedDiffValue<T>(op, ts, tc, tmp);
+        emitMask |= (r == 1 ? 1u : 0u) << 17;
+        zeroOrig |= r == 2;
+    }
+    if (__ballot(zeroOrig) != 0 && lane == 0) {
+        atomicOr(errWord, 1u);
+    }
+
+    // Wave scan of the per-lane counts, one ticket per chunk
+    u32 mine = __popc(emitMask);
+    u32 scan = mine;
+    for (u32 off = 1; off < 64; off <<= 1) {
+        u32 up = (u32)__shfl_up((int)scan, (int)off);
+        if (lane >= off) {
+            scan += up;
+        }
+    }
+    u32 waveTotal = (u32)__shfl((int)scan, 63);
+    if (waveTotal == 0) {
+        return;
+    }
+    u32 base = 0;
+    if (lane == 63) {
+        base = atomicAdd(ticket, waveTotal);
+    }
+    base = (u32)__shfl((int)base, 63);
+    u32 out = base + (scan - mine);
+
+    // Pass 2: emit {index relative to the region start, value}
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        T sv[E];
+        T cv[E];
+        __builtin_memcpy(sv, &s[k], 16);
+        __builtin_memcpy(cv, &c[k], 16);
+        u64 vecByte = alo + (u64)(lane + 64 * k) * 16;
+#pragma unroll
+        for (u32 e = 0; e < E; e++) {
+            if (emitMask & (1u << (k * E + e))) {
+                typedDiffValue<T>(op, sv[e], cv[e], tmp);
+                idxOut[out] =
+                  (u32)((vecByte - regionStart) / sizeof(T)) + e;
+                valOut[out] = tmp;
+                out++;
+            }
+        }
+    }
+    if (emitMask & (1u << 16)) {
+        typedDiffValue<T>(op, hs, hc, tmp);
+        idxOut[out] = (u32)((lo - regionStart) / sizeof(T)) + lane;
+        valOut[out] = tmp;
+        out++;
+    }
+    if (emitMask & (1u << 17)) {
+        typedDiffValue<T>(op, ts, tc, tmp);
+        idxOut[out] = (u32)((ahi - regionStart) / sizeof(T)) + lane;
+        valOut[out] = tmp;
+        out++;
+    }
+}
+
+template<typename T>
+__global__ __launch_bounds__(FAM_KERNEL_BLOCK) void applyTypedElemsKernel(
+  T* __restrict__ base,
+  const u32* __restrict__ idx,
+  const T* __restrict__ val,
+  u32 count,
+  int famOp)
+{
+    u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < count) {
+        T* p = base + idx[i];
+        *p = famApply<T>(famOp, *p, val[i]);
+    }
+}
+
+// SnapshotMergeOperation code -> FamOp, -1 where there is no typed merge
+inline int famOpForMerge(int op)
+{
+    switch (op) {
+        case FAM_MERGE_SUM:
+            return FAM_OP_SUM;
+        case FAM_MERGE_PRODUCT:
+            return FAM_OP_PROD;
+        case FAM_MERGE_SUBTRACT:
+            return FAM_OP_SUB;
+        case FAM_MERGE_MAX:
+            return FAM_OP_MAX;
+        case FAM_MERGE_MIN:
+            return FAM_OP_MIN;
+    }
+    return -1;
+}
+
+// SnapshotDataType code -> element size, 0 where the type has no merges
+inline u32 typedElemSize(int dtype)
+{
+    switch (dtype) {
+        case 2: // Int
+        case 4: // Float
+            return 4;
+        case 3: // Long
+        case 5: // Double
+            return 8;
+    }
+    return 0;
+}
+
 inline u32 gridFor(u64 items)
 {
     // One element per lane, uncapped: a 2048-block grid-stride copy
@@ -780,6 +1045,119 @@ hipError_t famCommitPages(const void* srcHostMapped,
                        pageIdx,
                        nPages,
                        valueBytes);
+    return hipGetLastError();
+}
+
+// Typed diff with compaction of the region [regionStart, regionStart +
+// nElems * sizeof(T)) of cur against snap. dtype is a SnapshotDataType
+// code (Int, Long, Float, Double), op a SnapshotMergeOperation code (Sum,
+// Product, Subtract, Max, Min). ticketDev and errDev are zeroed by the
+// caller; after the stream drains *ticketDev is the entry count and
+// *errDev is non-zero if a Product element had a zero original.
+hipError_t famTypedDiff(const void* snap,
+                        const void* cur,
+                        uint64_t regionStart,
+                        uint64_t nElems,
+                        int dtype,
+                        int op,
+                        uint32_t* ticketDev,
+                        uint32_t* errDev,
+                        uint32_t* idxOutDev,
+                        void* valOutDev,
+                        hipStream_t stream)
+{
+    u32 elem = typedElemSize(dtype);
+    if (elem == 0 || famOpForMerge(op) < 0 || (regionStart % elem) != 0 ||
+        nElems > 0xffffffffull ||
+        (((uintptr_t)snap | (uintptr_t)cur) & 15) != 0) {
+        return hipErrorInvalidValue;
+    }
+    if (nElems == 0) {
+        return hipSuccess;
+    }
+    u64 regionEnd = regionStart + nElems * elem;
+    u64 nChunks = (regionEnd - 1) / FAM_PAGE - regionStart / FAM_PAGE + 1;
+    u64 wavesPerBlock = FAM_KERNEL_BLOCK / 64;
+    u64 blocks = (nChunks + wavesPerBlock - 1) / wavesPerBlock;
+    // One wave per chunk, uncapped like the page diff (see famDiffXorPages)
+    dim3 grid((u32)blocks);
+    dim3 block(FAM_KERNEL_BLOCK);
+    const u8* s = (const u8*)snap;
+    const u8* c = (const u8*)cur;
+    switch (dtype) {
+        case 2:
+            hipLaunchKernelGGL(typedDiffKernel<int32_t>,
+                               grid, block, 0, stream,
+                               s, c, regionStart, regionEnd, op, ticketDev,
+                               errDev, idxOutDev, (int32_t*)valOutDev);
+            break;
+        case 3:
+            hipLaunchKernelGGL(typedDiffKernel<int64_t>,
+                               grid, block, 0, stream,
+                               s, c, regionStart, regionEnd, op, ticketDev,
+                               errDev, idxOutDev, (int64_t*)valOutDev);
+            break;
+        case 4:
+            hipLaunchKernelGGL(typedDiffKernel<float>,
+                               grid, block, 0, stream,
+                               s, c, regionStart, regionEnd, op, ticketDev,
+                               errDev, idxOutDev, (float*)valOutDev);
+            break;
+        default:
+            hipLaunchKernelGGL(typedDiffKernel<double>,
+                               grid, block, 0, stream,
+                               s, c, regionStart, regionEnd, op, ticketDev,
+                               errDev, idxOutDev, (double*)valOutDev);
+    }
+    return hipGetLastError();
+}
+
+// base[idx[i]] = op(base[idx[i]], val[i]) for i < count; base points at the
+// region start and must be aligned to the element. The caller has checked
+// every index against the allocation.
+hipError_t famApplyTypedElems(void* base,
+                              const uint32_t* idxDev,
+                              const void* valDev,
+                              uint32_t count,
+                              int dtype,
+                              int op,
+                              hipStream_t stream)
+{
+    u32 elem = typedElemSize(dtype);
+    int famOp = famOpForMerge(op);
+    if (elem == 0 || famOp < 0 || ((uintptr_t)base % elem) != 0) {
+        return hipErrorInvalidValue;
+    }
+    if (count == 0) {
+        return hipSuccess;
+    }
+    dim3 grid(gridFor(count));
+    dim3 block(FAM_KERNEL_BLOCK);
+    switch (dtype) {
+        case 2:
+            hipLaunchKernelGGL(applyTypedElemsKernel<int32_t>,
+                               grid, block, 0, stream,
+                               (int32_t*)base, idxDev,
+                               (const int32_t*)valDev, count, famOp);
+            break;
+        case 3:
+            hipLaunchKernelGGL(applyTypedElemsKernel<int64_t>,
+                               grid, block, 0, stream,
+                               (int64_t*)base, idxDev,
+                               (const int64_t*)valDev, count, famOp);
+            break;
+        case 4:
+            hipLaunchKernelGGL(applyTypedElemsKernel<float>,
+                               grid, block, 0, stream,
+                               (float*)base, idxDev,
+                               (const float*)valDev, count, famOp);
+            break;
+        default:
+            hipLaunchKernelGGL(applyTypedElemsKernel<double>,
+                               grid, block, 0, stream,
+                               (double*)base, idxDev,
+                               (const double*)valDev, count, famOp);
+    }
     return hipGetLastError();
 }
 

@@ -13,10 +13,13 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <optional>
 #include <string>
 #include <vector>
 
 #include <hip/hip_runtime.h>
+
+#include "faabricamd/snapshot.h"
 
 namespace faabricamd {
 
@@ -93,6 +96,42 @@ hipError_t famElementwiseOp(void* inout,
                             int dtype,
                             int op,
                             hipStream_t stream);
+// Typed merge regions. dtype is a SnapshotDataType code (Int, Long, Float,
+// Double) and op a SnapshotMergeOperation code (Sum, Product, Subtract,
+// Max, Min); anything else is hipErrorInvalidValue.
+//
+// famTypedDiff (typedDiffKernel): compacted typed diff of nElems elements
+// at byte regionStart (a multiple of the element size) of cur against
+// snap, both 16 B-aligned. An element is changed when !(orig == cur);
+// each changed one appends {index relative to the region start, value} to
+// idxOutDev/valOutDev (room for nElems entries, order unspecified), where
+// value is cur - orig (Sum), orig - cur (Subtract), cur / orig (Product)
+// or cur (Max, Min). *ticketDev and *errDev are zeroed by the caller:
+// afterwards the ticket is the entry count and the error word is non-zero
+// if a changed Product element had a zero original (nothing is emitted
+// for it).
+hipError_t famTypedDiff(const void* snap,
+                        const void* cur,
+                        uint64_t regionStart,
+                        uint64_t nElems,
+                        int dtype,
+                        int op,
+                        uint32_t* ticketDev,
+                        uint32_t* errDev,
+                        uint32_t* idxOutDev,
+                        void* valOutDev,
+                        hipStream_t stream);
+// famApplyTypedElems (applyTypedElemsKernel): base[idx[i]] =
+// op(base[idx[i]], val[i]) for i < count, base being the region start.
+// Max/Min keep std::max/std::min(target, value) operand order. The caller
+// has checked every index; count == 0 launches nothing.
+hipError_t famApplyTypedElems(void* base,
+                              const uint32_t* idxDev,
+                              const void* valDev,
+                              uint32_t count,
+                              int dtype,
+                              int op,
+                              hipStream_t stream);
 }
 
 inline constexpr size_t DEVICE_PAGE = 4096;
@@ -140,8 +179,38 @@ class DeviceSnapshot
                                   const uint8_t* payload,
                                   size_t payloadBytes);
 
-    // Queued packed diffs (wire form: [u32 n][u32 pages[n]][n*4KiB]) from
-    // remote/other-thread merges, applied at join time
+    // --- typed merge regions (Sum/Subtract/Product/Max/Min over
+    // Int/Long/Float/Double; see SnapshotMergeOperation::TypedElems) ---
+    // These three methods may be called from several threads on one
+    // snapshot: they take one lock between them. The page-diff methods
+    // above (diffXor, gatherLastDiffToHost, applyLastDiff, ...) keep their
+    // unlocked shared scratch, so a caller must not run those, or the
+    // join-time queue drain, concurrently with anything else on the
+    // same snapshot.
+
+    // Typed diff of one region of devPtr vs the snapshot, as the packed
+    // TypedElems diff; nothing when no element changed. The region ends at
+    // offset + length, or at the snapshot's end when length == 0; trailing
+    // bytes that do not fill an element are not diffed. Throws on a
+    // Product element with a zero original.
+    std::optional<SnapshotDiff> typedDiff(const void* devPtr,
+                                          const SnapshotMergeRegion& region);
+    // Validate (validateTypedElemsDiff), upload and merge a TypedElems
+    // diff into the snapshot
+    void applyTypedDiff(const SnapshotDiff& diff);
+    // The full thread diff of devPtr vs the snapshot under merge regions:
+    // one TypedElems diff per typed region that changed, plus one XorPages
+    // diff for everything else (typed bytes zeroed in its payload, pages
+    // wholly inside typed regions dropped). Leaves the filtered page list
+    // as the last diff.
+    std::vector<SnapshotDiff> diffWithRegions(
+      const void* devPtr,
+      const std::vector<SnapshotMergeRegion>& regions);
+
+    // Queued XorPages / TypedElems diffs from remote/other-thread merges,
+    // applied in arrival order at join time. queuePackedDiff takes the
+    // XorPages wire form ([u32 n][u32 pages[n]][n*4KiB]) bare.
+    void queueDiff(SnapshotDiff diff);
     void queuePackedDiff(std::vector<uint8_t> packed);
     int applyQueuedPackedDiffs();
 
@@ -152,6 +221,7 @@ class DeviceSnapshot
 
   private:
     void ensureDiffBuffers();
+    void ensureTypedScratch(size_t count, size_t elemSize);
 
     size_t bytes_ = 0;
     int device_ = 0;
@@ -167,9 +237,29 @@ class DeviceSnapshot
     uint32_t* bitmap_ = nullptr;
     uint32_t lastDirty_ = 0;
 
+    // Typed diff/apply scratch, grown to the largest region seen:
+    // {ticket, error word}, element indices, values
+    uint32_t* typedCtl_ = nullptr;
+    uint32_t* typedIdx_ = nullptr;
+    uint8_t* typedVal_ = nullptr;
+    size_t typedIdxCap_ = 0;
+    size_t typedValCap_ = 0;
+    // typedDiff, applyTypedDiff and diffWithRegions share this scratch and
+    // the stream: they serialise on one (recursive) lock
+    std::recursive_mutex typedMx_;
+
     std::mutex queueMx_;
-    std::vector<std::vector<uint8_t>> queuedPacked_;
+    std::vector<SnapshotDiff> queued_;
 };
+
+// Check the merge regions of a THREADS fork over a device arena of
+// arenaSize bytes and return the typed ones sorted by offset. A typed op
+// (Sum..Min) needs a typed element type, an element-aligned offset inside
+// the arena and no overlap with another typed region; Bytewise and XOR
+// over Raw mean default XOR paging. Anything else throws.
+std::vector<SnapshotMergeRegion> validateDeviceMergeRegions(
+  const std::vector<SnapshotMergeRegion>& regions,
+  size_t arenaSize);
 
 // Registry of HBM-resident snapshots (device analog of SnapshotRegistry)
 class DeviceSnapshotRegistry
@@ -183,9 +273,16 @@ class DeviceSnapshotRegistry
     void deleteSnapshot(const std::string& key);
     void clear();
 
+    // Merge regions of a fork travel by key, not on the snapshot object
+    // (an empty list erases; none set reads as empty)
+    void setMergeRegions(const std::string& key,
+                         const std::vector<SnapshotMergeRegion>& regions);
+    std::vector<SnapshotMergeRegion> getMergeRegions(const std::string& key);
+
   private:
     std::mutex mx;
     std::map<std::string, std::shared_ptr<DeviceSnapshot>> snapshots;
+    std::map<std::string, std::vector<SnapshotMergeRegion>> mergeRegions;
 };
 
 // Elementwise op on device buffers: inout = op(inout, in)

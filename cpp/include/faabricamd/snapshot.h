@@ -52,6 +52,12 @@ enum class SnapshotMergeOperation : int32_t
     // Packed page form used by the GPU THREADS flow (this project's own
     // extension): data = [u32 n][u32 pageIdx[n]][n x 4 KiB XOR payloads]
     XorPages = 7,
+    // Packed element form of a typed merge region on the GPU THREADS flow
+    // (this project's own extension): dataType = element type, offset =
+    // the region's byte offset, data = [u32 op][u32 count]
+    // [u32 elemIdx[count]][zero pad to 8 B][T value[count]], little-endian,
+    // where op is the real merge operation (Sum..Min)
+    TypedElems = 8,
 };
 
 struct SnapshotDiff
@@ -79,6 +85,30 @@ struct SnapshotDiff
     SnapshotDiffMsg toMsg() const;
     static SnapshotDiff fromMsg(const SnapshotDiffMsg& msg);
 };
+
+// sizeof(T) of a typed-merge element type (Int, Long, Float, Double), 0 for
+// the others
+size_t snapshotTypedElemSize(SnapshotDataType dataType);
+bool isTypedMergeOperation(SnapshotMergeOperation op);
+
+// A validated view into a TypedElems diff's data
+struct TypedElemsView
+{
+    SnapshotMergeOperation op = SnapshotMergeOperation::Sum;
+    uint32_t count = 0;
+    size_t elemSize = 0;
+    const uint8_t* idx = nullptr;    // count x u32
+    const uint8_t* values = nullptr; // count x elemSize, 8 B-aligned offset
+};
+
+size_t typedElemsPackedSize(uint32_t count, size_t elemSize);
+
+// The one validator of the TypedElems wire form, run by every consumer
+// before anything is uploaded or applied: exact size for the count, a
+// typed op and element type, an element-aligned offset and every element
+// inside snapshotSize. Throws FaabricException on a violation.
+TypedElemsView validateTypedElemsDiff(const SnapshotDiff& diff,
+                                      size_t snapshotSize);
 
 struct SnapshotMergeRegion
 {
@@ -218,6 +248,10 @@ enum class SnapshotCalls : uint8_t
     // Device (HBM) snapshot as host bytes — our extension beyond the
     // reference's flatbuffers surface, so it rides its own call
     PushSnapshotDevice = 6,
+    // Merge regions of a device snapshot, stored by key (the IPC landing
+    // path creates the snapshot object on its first chunk, so the object
+    // cannot carry them): body is a SnapshotPushRequest with no contents
+    DeviceMergeRegions = 7,
 };
 
 class SnapshotServer : public MessageEndpointServer
@@ -244,6 +278,11 @@ class SnapshotClient : public MessageEndpointClient
     void pushDeviceSnapshotFromDevice(const std::string& key,
                                       const void* devPtr,
                                       size_t size);
+    // Sent before the device snapshot itself, so a remote thread that
+    // waited for the snapshot finds its regions
+    void pushDeviceMergeRegions(
+      const std::string& key,
+      const std::vector<SnapshotMergeRegion>& regions);
     void pushSnapshotUpdate(const std::string& key,
                             const std::vector<SnapshotDiff>& diffs,
                             const std::vector<SnapshotMergeRegion>& regions);

@@ -330,14 +330,13 @@ std::vector<std::pair<int32_t, int32_t>> Executor::executeThreads(
     std::shared_ptr<DeviceSnapshot> dsnap;
     if (onDevice) {
         // GPU fork-join: the snapshot lives in HBM; diffs are XOR page
-        // diffs from the gfx950 kernels (typed merge regions are a host
-        // feature — reject them loudly rather than silently ignoring)
-        if (!mergeRegions.empty()) {
-            throw FaabricException(
-              "typed merge regions unsupported on the device arena "
-              "(XOR page diffing applies)");
-        }
+        // diffs from the gfx950 kernels, plus typed element diffs for
+        // the typed merge regions. A region the device path cannot
+        // honour is rejected here, before anything is dispatched
+        validateDeviceMergeRegions(mergeRegions, deviceArenaSize);
         auto& dreg = DeviceSnapshotRegistry::get();
+        // The regions travel by key; the diffing threads read them there
+        dreg.setMergeRegions(key, mergeRegions);
         if (dreg.snapshotExists(key) &&
             dreg.getSnapshot(key)->size() == deviceArenaSize) {
             dsnap = dreg.getSnapshot(key);
@@ -386,6 +385,8 @@ std::vector<std::pair<int32_t, int32_t>> Executor::executeThreads(
     // Ship the snapshot to the other hosts in the (updated) decision —
     // the planner cannot: the snapshot lives here, not in its registry
     lastForkSnapshotKey = key;
+    // Remote hosts sent this fork's merge regions (device arena only)
+    std::vector<std::string> regionHosts;
     {
         const std::string& thisHost = getSystemConfig().endpointHost;
         for (const auto& host : decision->uniqueHosts()) {
@@ -398,6 +399,14 @@ std::vector<std::pair<int32_t, int32_t>> Executor::executeThreads(
                 lastForkRemoteHosts.push_back(host);
             }
             if (onDevice) {
+                // Regions first: a remote thread waits in restore() for
+                // the snapshot, so they are there when it diffs. A fork
+                // without regions sends nothing
+                if (!mergeRegions.empty()) {
+                    getSnapshotClient(host)->pushDeviceMergeRegions(
+                      key, mergeRegions);
+                    regionHosts.push_back(host);
+                }
                 // Same-node workers stream this over xGMI (HIP IPC);
                 // only cross-node peers fall back to a host copy
                 getSnapshotClient(host)->pushDeviceSnapshotFromDevice(
@@ -439,6 +448,19 @@ std::vector<std::pair<int32_t, int32_t>> Executor::executeThreads(
         if (err != hipSuccess ||
             hipStreamSynchronize(nullptr) != hipSuccess) {
             throw FaabricException("device snapshot merge-back failed");
+        }
+        // As the host path's clearMergeRegions, here and on every host
+        // the regions went to: a later fork without regions must find
+        // none anywhere
+        DeviceSnapshotRegistry::get().setMergeRegions(key, {});
+        for (const auto& host : regionHosts) {
+            try {
+                getSnapshotClient(host)->pushDeviceMergeRegions(key, {});
+            } catch (const std::exception& e) {
+                FAM_WARN("clearing merge regions on %s failed: %s",
+                         host.c_str(),
+                         e.what());
+            }
         }
     } else {
         snap->writeQueuedDiffs();
@@ -629,7 +651,16 @@ void Executor::handleTaskResult(Message& msg,
             // snapshot, ship the compact XOR page diff
             auto dsnap =
               DeviceSnapshotRegistry::get().getSnapshot(req->snapshotKey);
-            uint32_t nd = dsnap->diffXor(deviceArena);
+            auto regions = DeviceSnapshotRegistry::get().getMergeRegions(
+              req->snapshotKey);
+            uint32_t nd = 0;
+            if (!regions.empty()) {
+                // Typed element diffs for the typed regions, XOR pages
+                // for the rest
+                threadDiffs = dsnap->diffWithRegions(deviceArena, regions);
+            } else {
+                nd = dsnap->diffXor(deviceArena);
+            }
             if (nd > 0) {
                 std::vector<uint32_t> pages;
                 std::vector<uint8_t> payload;
@@ -700,7 +731,7 @@ void Executor::handleTaskResult(Message& msg,
                         auto dsnap = DeviceSnapshotRegistry::get()
                                        .getSnapshot(req->snapshotKey);
                         for (auto& d : threadDiffs) {
-                            dsnap->queuePackedDiff(d.dataCopy);
+                            dsnap->queueDiff(d);
                         }
                     } else {
                         auto snap = SnapshotRegistry::get().getSnapshot(

@@ -4,6 +4,7 @@
 #include "faabricamd/ops.h"
 #include "faabricamd/util.h"
 
+#include <algorithm>
 #include <cstring>
 
 namespace faabricamd {
@@ -69,6 +70,15 @@ DeviceSnapshot::~DeviceSnapshot()
     }
     if (bitmap_ != nullptr) {
         hipFree(bitmap_);
+    }
+    if (typedCtl_ != nullptr) {
+        hipFree(typedCtl_);
+    }
+    if (typedIdx_ != nullptr) {
+        hipFree(typedIdx_);
+    }
+    if (typedVal_ != nullptr) {
+        hipFree(typedVal_);
     }
     if (stream_ != nullptr) {
         hipStreamDestroy(stream_);
@@ -244,20 +254,325 @@ void DeviceSnapshot::applyCompactDiffFromHost(
     hipFree(payloadDev);
 }
 
+// ------------------------- typed merge regions -------------------------------
+
+std::vector<SnapshotMergeRegion> validateDeviceMergeRegions(
+  const std::vector<SnapshotMergeRegion>& regions,
+  size_t arenaSize)
+{
+    std::vector<SnapshotMergeRegion> typed;
+    for (const auto& r : regions) {
+        if (r.operation == SnapshotMergeOperation::Bytewise ||
+            r.operation == SnapshotMergeOperation::XOR) {
+            if (r.dataType != SnapshotDataType::Raw) {
+                throw FaabricException(
+                  "device merge region: Bytewise/XOR need the Raw type");
+            }
+            continue; // default XOR paging
+        }
+        if (!isTypedMergeOperation(r.operation)) {
+            throw FaabricException(
+              "device merge region: not a region operation");
+        }
+        size_t elem = snapshotTypedElemSize(r.dataType);
+        if (elem == 0) {
+            throw FaabricException(
+              "device merge region: typed operation needs Int, Long, "
+              "Float or Double");
+        }
+        if ((r.offset % elem) != 0) {
+            throw FaabricException("device merge region: unaligned offset");
+        }
+        if ((size_t)r.offset >= arenaSize) {
+            throw FaabricException(
+              "device merge region: offset outside the arena");
+        }
+        typed.push_back(r);
+    }
+    std::sort(typed.begin(),
+              typed.end(),
+              [](const SnapshotMergeRegion& a, const SnapshotMergeRegion& b) {
+                  return a.offset < b.offset;
+              });
+    auto endOf = [arenaSize](const SnapshotMergeRegion& r) {
+        return r.length == 0
+                 ? arenaSize
+                 : std::min(arenaSize, (size_t)r.offset + r.length);
+    };
+    for (size_t i = 1; i < typed.size(); i++) {
+        if (endOf(typed[i - 1]) > (size_t)typed[i].offset) {
+            throw FaabricException(
+              "device merge region: typed regions overlap");
+        }
+    }
+    return typed;
+}
+
+void DeviceSnapshot::ensureTypedScratch(size_t count, size_t elemSize)
+{
+    if (typedCtl_ == nullptr) {
+        OPS_HIP_CHECK(hipMalloc(&typedCtl_, 2 * sizeof(uint32_t)));
+    }
+    if (count > typedIdxCap_) {
+        if (typedIdx_ != nullptr) {
+            hipFree(typedIdx_);
+            typedIdx_ = nullptr;
+            typedIdxCap_ = 0;
+        }
+        OPS_HIP_CHECK(hipMalloc(&typedIdx_, count * sizeof(uint32_t)));
+        typedIdxCap_ = count;
+    }
+    if (count * elemSize > typedValCap_) {
+        if (typedVal_ != nullptr) {
+            hipFree(typedVal_);
+            typedVal_ = nullptr;
+            typedValCap_ = 0;
+        }
+        OPS_HIP_CHECK(hipMalloc(&typedVal_, count * elemSize));
+        typedValCap_ = count * elemSize;
+    }
+}
+
+std::optional<SnapshotDiff> DeviceSnapshot::typedDiff(
+  const void* devPtr,
+  const SnapshotMergeRegion& region)
+{
+    size_t elem = snapshotTypedElemSize(region.dataType);
+    if (elem == 0 || !isTypedMergeOperation(region.operation)) {
+        throw FaabricException("typed diff: not a typed merge region");
+    }
+    if ((region.offset % elem) != 0) {
+        throw FaabricException("typed diff: unaligned region offset");
+    }
+    if ((size_t)region.offset >= bytes_) {
+        throw FaabricException("typed diff: region outside the snapshot");
+    }
+    size_t end = region.length == 0
+                   ? bytes_
+                   : std::min(bytes_, (size_t)region.offset + region.length);
+    // Trailing bytes that do not fill an element are diffed by nothing
+    size_t nElems = (end - region.offset) / elem;
+    if (nElems == 0) {
+        return std::nullopt;
+    }
+    if (nElems > 0xffffffffull) {
+        throw FaabricException("typed diff: region too large");
+    }
+
+    std::lock_guard<std::recursive_mutex> lock(typedMx_);
+    OPS_HIP_CHECK(hipSetDevice(device_));
+    ensureTypedScratch(nElems, elem);
+    OPS_HIP_CHECK(
+      hipMemsetAsync(typedCtl_, 0, 2 * sizeof(uint32_t), stream_));
+    OPS_HIP_CHECK(famTypedDiff(snap_,
+                               devPtr,
+                               region.offset,
+                               nElems,
+                               (int)region.dataType,
+                               (int)region.operation,
+                               typedCtl_,
+                               typedCtl_ + 1,
+                               typedIdx_,
+                               typedVal_,
+                               stream_));
+    uint32_t ctl[2] = { 0, 0 };
+    OPS_HIP_CHECK(hipMemcpyAsync(
+      ctl, typedCtl_, sizeof(ctl), hipMemcpyDeviceToHost, stream_));
+    OPS_HIP_CHECK(hipStreamSynchronize(stream_));
+    if (ctl[1] != 0) {
+        throw FaabricException("product diff with zero original");
+    }
+    uint32_t count = ctl[0];
+    if (count == 0) {
+        return std::nullopt;
+    }
+    if (count > nElems) {
+        throw FaabricException("typed diff: entry count past the region");
+    }
+
+    SnapshotDiff diff;
+    diff.dataType = region.dataType;
+    diff.operation = SnapshotMergeOperation::TypedElems;
+    diff.offset = region.offset;
+    diff.dataCopy.assign(typedElemsPackedSize(count, elem), 0);
+    uint32_t op = (uint32_t)region.operation;
+    std::memcpy(diff.dataCopy.data(), &op, 4);
+    std::memcpy(diff.dataCopy.data() + 4, &count, 4);
+    OPS_HIP_CHECK(hipMemcpyAsync(diff.dataCopy.data() + 8,
+                                 typedIdx_,
+                                 (size_t)count * 4,
+                                 hipMemcpyDeviceToHost,
+                                 stream_));
+    OPS_HIP_CHECK(hipMemcpyAsync(
+      diff.dataCopy.data() + diff.dataCopy.size() - (size_t)count * elem,
+      typedVal_,
+      (size_t)count * elem,
+      hipMemcpyDeviceToHost,
+      stream_));
+    OPS_HIP_CHECK(hipStreamSynchronize(stream_));
+    return diff;
+}
+
+void DeviceSnapshot::applyTypedDiff(const SnapshotDiff& diff)
+{
+    if (diff.operation != SnapshotMergeOperation::TypedElems) {
+        throw FaabricException("not a typed elems diff");
+    }
+    // Nothing is uploaded or applied before the whole diff is checked
+    TypedElemsView v = validateTypedElemsDiff(diff, bytes_);
+    if (v.count == 0) {
+        return;
+    }
+    std::lock_guard<std::recursive_mutex> lock(typedMx_);
+    OPS_HIP_CHECK(hipSetDevice(device_));
+    ensureTypedScratch(v.count, v.elemSize);
+    OPS_HIP_CHECK(hipMemcpyAsync(typedIdx_,
+                                 v.idx,
+                                 (size_t)v.count * 4,
+                                 hipMemcpyHostToDevice,
+                                 stream_));
+    OPS_HIP_CHECK(hipMemcpyAsync(typedVal_,
+                                 v.values,
+                                 (size_t)v.count * v.elemSize,
+                                 hipMemcpyHostToDevice,
+                                 stream_));
+    OPS_HIP_CHECK(famApplyTypedElems(snap_ + diff.offset,
+                                     typedIdx_,
+                                     typedVal_,
+                                     v.count,
+                                     (int)diff.dataType,
+                                     (int)v.op,
+                                     stream_));
+    OPS_HIP_CHECK(hipStreamSynchronize(stream_));
+}
+
+std::vector<SnapshotDiff> DeviceSnapshot::diffWithRegions(
+  const void* devPtr,
+  const std::vector<SnapshotMergeRegion>& regions)
+{
+    std::vector<SnapshotMergeRegion> typed =
+      validateDeviceMergeRegions(regions, bytes_);
+    std::lock_guard<std::recursive_mutex> lock(typedMx_);
+
+    std::vector<SnapshotDiff> diffs;
+    for (const auto& r : typed) {
+        auto d = typedDiff(devPtr, r);
+        if (d.has_value()) {
+            diffs.push_back(std::move(*d));
+        }
+    }
+
+    // Everything else ships as XOR pages, with the typed bytes taken out:
+    // their change already travels as a typed diff
+    uint32_t nd = diffXor(devPtr);
+    if (nd == 0) {
+        return diffs;
+    }
+    if (!typed.empty()) {
+        // Typed byte ranges [begin, end), sorted; touching ones merged so
+        // a page covered by two adjacent regions counts as wholly typed
+        std::vector<std::pair<size_t, size_t>> ranges;
+        for (const auto& r : typed) {
+            size_t end = r.length == 0
+                           ? bytes_
+                           : std::min(bytes_, (size_t)r.offset + r.length);
+            // The sparse payload is indexed by page, so arena offsets
+            // apply directly
+            OPS_HIP_CHECK(hipMemsetAsync(
+              payload_ + r.offset, 0, end - r.offset, stream_));
+            if (!ranges.empty() && ranges.back().second == r.offset) {
+                ranges.back().second = end;
+            } else {
+                ranges.emplace_back(r.offset, end);
+            }
+        }
+        std::vector<uint32_t> pages(nd);
+        OPS_HIP_CHECK(hipMemcpyAsync(pages.data(),
+                                     pageIdx_,
+                                     (size_t)nd * 4,
+                                     hipMemcpyDeviceToHost,
+                                     stream_));
+        OPS_HIP_CHECK(hipStreamSynchronize(stream_));
+        std::vector<uint32_t> kept;
+        kept.reserve(nd);
+        for (uint32_t p : pages) {
+            size_t pLo = (size_t)p * DEVICE_PAGE;
+            size_t pHi = pLo + DEVICE_PAGE;
+            bool whollyTyped = false;
+            for (const auto& [lo, hi] : ranges) {
+                if (lo <= pLo && pHi <= hi) {
+                    whollyTyped = true;
+                    break;
+                }
+            }
+            if (!whollyTyped) {
+                kept.push_back(p);
+            }
+        }
+        if (!kept.empty()) {
+            OPS_HIP_CHECK(hipMemcpyAsync(pageIdx_,
+                                         kept.data(),
+                                         kept.size() * 4,
+                                         hipMemcpyHostToDevice,
+                                         stream_));
+            OPS_HIP_CHECK(hipStreamSynchronize(stream_));
+        }
+        lastDirty_ = (uint32_t)kept.size();
+        if (kept.empty()) {
+            return diffs;
+        }
+    }
+
+    std::vector<uint32_t> pages;
+    std::vector<uint8_t> payload;
+    gatherLastDiffToHost(pages, payload);
+    uint32_t n = (uint32_t)pages.size();
+    SnapshotDiff xd;
+    xd.dataType = SnapshotDataType::Raw;
+    xd.operation = SnapshotMergeOperation::XorPages;
+    xd.offset = 0;
+    xd.dataCopy.resize(4 + (size_t)n * 4 + payload.size());
+    std::memcpy(xd.dataCopy.data(), &n, 4);
+    std::memcpy(xd.dataCopy.data() + 4, pages.data(), (size_t)n * 4);
+    std::memcpy(
+      xd.dataCopy.data() + 4 + (size_t)n * 4, payload.data(), payload.size());
+    diffs.push_back(std::move(xd));
+    return diffs;
+}
+
+void DeviceSnapshot::queueDiff(SnapshotDiff diff)
+{
+    if (diff.operation != SnapshotMergeOperation::XorPages &&
+        diff.operation != SnapshotMergeOperation::TypedElems) {
+        throw FaabricException(
+          "device snapshots queue XorPages and TypedElems diffs only");
+    }
+    std::lock_guard<std::mutex> lock(queueMx_);
+    queued_.push_back(std::move(diff));
+}
+
 void DeviceSnapshot::queuePackedDiff(std::vector<uint8_t> packed)
 {
-    std::lock_guard<std::mutex> lock(queueMx_);
-    queuedPacked_.push_back(std::move(packed));
+    SnapshotDiff d;
+    d.dataType = SnapshotDataType::Raw;
+    d.operation = SnapshotMergeOperation::XorPages;
+    d.dataCopy = std::move(packed);
+    queueDiff(std::move(d));
 }
 
 int DeviceSnapshot::applyQueuedPackedDiffs()
 {
-    std::vector<std::vector<uint8_t>> toApply;
+    std::vector<SnapshotDiff> toApply;
     {
         std::lock_guard<std::mutex> lock(queueMx_);
-        toApply.swap(queuedPacked_);
+        toApply.swap(queued_);
     }
-    for (const auto& packed : toApply) {
+    for (const auto& diff : toApply) {
+        if (diff.operation == SnapshotMergeOperation::TypedElems) {
+            applyTypedDiff(diff);
+            continue;
+        }
+        const std::vector<uint8_t>& packed = diff.dataCopy;
         if (packed.size() < 4) {
             continue;
         }
@@ -311,12 +626,37 @@ void DeviceSnapshotRegistry::deleteSnapshot(const std::string& key)
 {
     std::lock_guard<std::mutex> lock(mx);
     snapshots.erase(key);
+    mergeRegions.erase(key);
 }
 
 void DeviceSnapshotRegistry::clear()
 {
     std::lock_guard<std::mutex> lock(mx);
     snapshots.clear();
+    mergeRegions.clear();
+}
+
+void DeviceSnapshotRegistry::setMergeRegions(
+  const std::string& key,
+  const std::vector<SnapshotMergeRegion>& regions)
+{
+    std::lock_guard<std::mutex> lock(mx);
+    if (regions.empty()) {
+        mergeRegions.erase(key);
+    } else {
+        mergeRegions[key] = regions;
+    }
+}
+
+std::vector<SnapshotMergeRegion> DeviceSnapshotRegistry::getMergeRegions(
+  const std::string& key)
+{
+    std::lock_guard<std::mutex> lock(mx);
+    auto it = mergeRegions.find(key);
+    if (it == mergeRegions.end()) {
+        return {};
+    }
+    return it->second;
 }
 
 void deviceElementwiseOp(void* inout,

@@ -163,6 +163,82 @@ static void applyDiffValue(uint8_t* targetPtr,
     std::memcpy(targetPtr, &target, sizeof(T));
 }
 
+// ------------------------- TypedElems wire form -----------------------------
+
+size_t snapshotTypedElemSize(SnapshotDataType dataType)
+{
+    switch (dataType) {
+        case SnapshotDataType::Int:
+        case SnapshotDataType::Float:
+            return 4;
+        case SnapshotDataType::Long:
+        case SnapshotDataType::Double:
+            return 8;
+        default:
+            return 0;
+    }
+}
+
+bool isTypedMergeOperation(SnapshotMergeOperation op)
+{
+    switch (op) {
+        case SnapshotMergeOperation::Sum:
+        case SnapshotMergeOperation::Subtract:
+        case SnapshotMergeOperation::Product:
+        case SnapshotMergeOperation::Max:
+        case SnapshotMergeOperation::Min:
+            return true;
+        default:
+            return false;
+    }
+}
+
+size_t typedElemsPackedSize(uint32_t count, size_t elemSize)
+{
+    size_t header = 8 + (size_t)count * 4;
+    header = (header + 7) & ~(size_t)7;
+    return header + (size_t)count * elemSize;
+}
+
+TypedElemsView validateTypedElemsDiff(const SnapshotDiff& diff,
+                                      size_t snapshotSize)
+{
+    TypedElemsView v;
+    v.elemSize = snapshotTypedElemSize(diff.dataType);
+    if (v.elemSize == 0) {
+        throw FaabricException("typed elems diff: untyped data type");
+    }
+    if (diff.size() < 8) {
+        throw FaabricException("typed elems diff: short buffer");
+    }
+    uint32_t op = 0;
+    std::memcpy(&op, diff.getData(), 4);
+    std::memcpy(&v.count, diff.getData() + 4, 4);
+    v.op = (SnapshotMergeOperation)op;
+    if (!isTypedMergeOperation(v.op)) {
+        throw FaabricException("typed elems diff: not a typed operation");
+    }
+    if (diff.size() != typedElemsPackedSize(v.count, v.elemSize)) {
+        throw FaabricException("typed elems diff: size does not match count");
+    }
+    if ((diff.offset % v.elemSize) != 0) {
+        throw FaabricException("typed elems diff: unaligned offset");
+    }
+    v.idx = diff.getData() + 8;
+    v.values = diff.getData() + diff.size() - (size_t)v.count * v.elemSize;
+    // Indices arrive off the wire (ThreadResult RPC): one past the
+    // snapshot would be a write past the allocation, host or HBM
+    for (uint32_t i = 0; i < v.count; i++) {
+        uint32_t e = 0;
+        std::memcpy(&e, v.idx + (size_t)i * 4, 4);
+        if ((uint64_t)diff.offset + ((uint64_t)e + 1) * v.elemSize >
+            (uint64_t)snapshotSize) {
+            throw FaabricException("typed elems diff: element out of range");
+        }
+    }
+    return v;
+}
+
 template<typename T>
 static void addTypedDiffs(std::vector<SnapshotDiff>& diffs,
                           SnapshotDataType dataType,
@@ -489,8 +565,46 @@ std::vector<SnapshotDiff> SnapshotData::diffWithMemory(const uint8_t* updated,
     return diffWithDirtyRegions(updated, updatedSize, allDirty);
 }
 
+template<typename T>
+static void applyTypedElems(uint8_t* base, const TypedElemsView& v)
+{
+    for (uint32_t i = 0; i < v.count; i++) {
+        uint32_t e = 0;
+        std::memcpy(&e, v.idx + (size_t)i * 4, 4);
+        applyDiffValue<T>(base + (size_t)e * sizeof(T),
+                          v.values + (size_t)i * sizeof(T),
+                          v.op);
+    }
+}
+
 void SnapshotData::applyDiff(const SnapshotDiff& diff)
 {
+    if (diff.operation == SnapshotMergeOperation::TypedElems) {
+        // Packed element form of a typed region (GPU THREADS flow):
+        // validate everything before the first write
+        TypedElemsView v = validateTypedElemsDiff(diff, maxSize_);
+        uint8_t* base = data_.data() + diff.offset;
+        for (uint32_t i = 0; i < v.count; i++) {
+            uint32_t e = 0;
+            std::memcpy(&e, v.idx + (size_t)i * 4, 4);
+            size_ = std::max(
+              size_, (size_t)diff.offset + ((size_t)e + 1) * v.elemSize);
+        }
+        switch (diff.dataType) {
+            case SnapshotDataType::Int:
+                applyTypedElems<int32_t>(base, v);
+                break;
+            case SnapshotDataType::Long:
+                applyTypedElems<int64_t>(base, v);
+                break;
+            case SnapshotDataType::Float:
+                applyTypedElems<float>(base, v);
+                break;
+            default:
+                applyTypedElems<double>(base, v);
+        }
+        return;
+    }
     if (diff.operation != SnapshotMergeOperation::XorPages &&
         diff.offset + diff.size() > maxSize_) {
         throw FaabricException("diff out of snapshot bounds");
@@ -714,6 +828,19 @@ std::string SnapshotServer::doSyncRecv(uint8_t code, const std::string& body)
                                                            dsnap);
             return {};
         }
+        case SnapshotCalls::DeviceMergeRegions: {
+            auto req = SnapshotPushRequest::decode(body);
+            std::vector<SnapshotMergeRegion> regions;
+            for (const auto& r : req.mergeRegions) {
+                regions.emplace_back((uint32_t)r.offset,
+                                     r.length,
+                                     (SnapshotDataType)r.dataType,
+                                     (SnapshotMergeOperation)r.mergeOp);
+            }
+            DeviceSnapshotRegistry::get().setMergeRegions(req.key,
+                                                          regions);
+            return {};
+        }
         case SnapshotCalls::PushSnapshotIpc: {
             // Streamed device snapshot: land the arena segment straight
             // in HBM (create the snapshot on the first chunk)
@@ -797,9 +924,10 @@ std::string SnapshotServer::doSyncRecv(uint8_t code, const std::string& body)
                     auto dsnap =
                       DeviceSnapshotRegistry::get().getSnapshot(req.key);
                     for (const auto& d : req.diffs) {
-                        if ((SnapshotMergeOperation)d.mergeOp ==
-                            SnapshotMergeOperation::XorPages) {
-                            dsnap->queuePackedDiff(d.data);
+                        auto op = (SnapshotMergeOperation)d.mergeOp;
+                        if (op == SnapshotMergeOperation::XorPages ||
+                            op == SnapshotMergeOperation::TypedElems) {
+                            dsnap->queueDiff(SnapshotDiff::fromMsg(d));
                         }
                     }
                 } else {
@@ -944,6 +1072,29 @@ void SnapshotClient::pushDeviceSnapshotFromDevice(const std::string& key,
         throw FaabricException("device snapshot copy-out failed");
     }
     pushDeviceSnapshot(key, hostCopy.data(), size);
+}
+
+void SnapshotClient::pushDeviceMergeRegions(
+  const std::string& key,
+  const std::vector<SnapshotMergeRegion>& regions)
+{
+    if (isMockMode()) {
+        std::lock_guard<std::mutex> lock(snapMockMx);
+        mockedPushes.emplace_back(getHost(), key);
+        return;
+    }
+    SnapshotPushRequest req;
+    req.key = key;
+    req.onDevice = true;
+    for (const auto& r : regions) {
+        SnapshotMergeRegionMsg m;
+        m.offset = (int32_t)r.offset;
+        m.length = r.length;
+        m.dataType = (int32_t)r.dataType;
+        m.mergeOp = (int32_t)r.operation;
+        req.mergeRegions.push_back(m);
+    }
+    syncSend((uint8_t)SnapshotCalls::DeviceMergeRegions, req.encode());
 }
 
 void SnapshotClient::pushSnapshotUpdate(
